@@ -12,8 +12,10 @@ records, 10-byte keys) so 8 GPUs sort exactly 1 TB; per-GPU work is fixed as N g
 
 One step = read the input table (synthetic generator store, materialised in HBM) -> sample ->
 range partition -> RCCL all-to-all-v over xGMI -> local LSD radix sort -> row gather into the
-output table.  Nothing is cached between steps; the output is validated valsort-style (global
-checksum, record count, in-rank order, cross-rank boundaries) after the timed region.
+output table.  Nothing is cached between steps.  A plain run sets up, warms up, times the steps
+and prints the result line; ``--full`` also validates the output valsort-style (global checksum,
+record count, in-rank order, cross-rank boundaries) outside the timed region, and
+``--dump-outputs DIR`` writes a fixed sample of the last step's sorted table as ``.npy`` files.
 
 ``--total-bytes B`` sizes the job by its total input instead (B / N per GPU, e.g. 1e12 = the
 BASELINE's 1 TB).  A per-GPU share past what one GPU sorts in HBM (IN_HBM_MAX_BYTES) runs the
@@ -50,6 +52,32 @@ def check_env(rehearsal: bool) -> dict:
     return {k: v for k, v in os.environ.items() if k.startswith("DRYAD_")}
 
 
+DUMP_EDGE_ROWS = 1024        # --dump-outputs: the first and last rows of the output table ...
+DUMP_SAMPLE_ROWS = 98304     # ... and this many rows between, drawn with a fixed seed (40 MB as float32)
+DUMP_SEED = 0x0D5EED
+
+
+def dump_outputs(path: str, out, world) -> None:
+    """``--dump-outputs DIR``: the sorted table the last timed step returned, as a fixed, seeded
+    sample of its rows (the row numbers depend only on the table's length, so two builds given the
+    same arguments write the same rows of the same input):
+    ``sorted_rows.npy`` float32 [k, 100] (record bytes) and ``sorted_rows_index.npy`` float64 [k]."""
+    import numpy as np
+    import torch
+    n = int(out.shape[0])
+    if n <= 2 * DUMP_EDGE_ROWS + DUMP_SAMPLE_ROWS:
+        idx = torch.arange(n, dtype=torch.int64)
+    else:
+        g = torch.Generator().manual_seed(DUMP_SEED)
+        mid = torch.randint(DUMP_EDGE_ROWS, n - DUMP_EDGE_ROWS, (DUMP_SAMPLE_ROWS,), generator=g, dtype=torch.int64)
+        idx = torch.cat([torch.arange(DUMP_EDGE_ROWS), torch.unique(mid), torch.arange(n - DUMP_EDGE_ROWS, n)])
+    rows = out[idx.to(out.device)].cpu().numpy().astype(np.float32)
+    os.makedirs(path, exist_ok=True)
+    tag = "" if world.size == 1 else f"_rank{world.rank}"
+    np.save(os.path.join(path, f"sorted_rows{tag}.npy"), rows)
+    np.save(os.path.join(path, f"sorted_rows_index{tag}.npy"), idx.numpy().astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -60,7 +88,14 @@ def main():
                     help="total input bytes over all GPUs (overrides --records-per-gpu); past the in-HBM "
                          "capacity per GPU the out-of-core path runs")
     ap.add_argument("--hbm-budget-gb", type=float, default=None, help="out-of-core path: HBM budget per GPU")
-    ap.add_argument("--no-validate", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the timed steps, check the output valsort-style (a generator pass for the input "
+                         "checksum before the steps, a checking pass over the output after them; exit 3 on a "
+                         "mismatch); a plain run only sets up, warms up, times the steps and reports")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last step computed as DIR/<name>.npy (float32 / "
+                         "float64): a fixed, seeded sample of the sorted output table's rows and their row numbers")
+    ap.add_argument("--no-validate", action="store_true", help="with --full: skip the output check")
     ap.add_argument("--direct", action="store_true",
                     help="run the sort pipeline directly instead of through the DryadLINQ query API")
     ap.add_argument("--rehearsal", action="store_true",
@@ -96,6 +131,10 @@ def main():
                          "at the full per-GPU size: the HBM working set and the RCCL path of an N-GPU run")
     args = ap.parse_args()
     env = check_env(args.rehearsal)
+    if args.dump_outputs and (args.loopback_ranks or args.input):
+        print("[bench] --dump-outputs takes the in-HBM sort's output table (no --loopback-ranks / --input)",
+              file=sys.stderr)
+        sys.exit(2)
     if args.loopback_ranks:
         return loopback(args, env)
 
@@ -118,6 +157,9 @@ def main():
     if args.total_bytes is not None:
         records = int(args.total_bytes / world.size) // RECORD
     ooc = records * RECORD > IN_HBM_MAX_BYTES
+    if args.dump_outputs and ooc:
+        print("[bench] --dump-outputs takes the in-HBM sort's output table (not the out-of-core path)", file=sys.stderr)
+        sys.exit(2)
     cfg = TeraSortConfig(records_per_rank=records)
     t_alloc = time.perf_counter()
     stored = args.input is not None
@@ -139,7 +181,7 @@ def main():
         print(f"[bench] allocated working set in {time.perf_counter() - t_alloc:.1f}s; HBM free {free/1e9:.1f} "
               f"/ {total/1e9:.1f} GB", file=sys.stderr, flush=True)
     expect = None
-    if not args.no_validate:
+    if args.full and not args.no_validate:
         expect = job.input_checksum()
         torch.cuda.empty_cache()
     for i in range(args.warmup):
@@ -149,6 +191,8 @@ def main():
         if world.rank == 0:
             print(f"[bench] warmup {i}: {time.perf_counter() - t0:.3f}s", file=sys.stderr, flush=True)
     secs = run_steps(job, args.steps)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, job.out, world)
     val = None
     if expect is not None:
         val = job.validate(*expect)

@@ -11,6 +11,7 @@ from __future__ import annotations
 import ctypes
 import os
 import threading
+import weakref
 from pathlib import Path
 
 import torch
@@ -147,10 +148,10 @@ def hip_runtime():
             _HIP = ctypes.CDLL("libamdhip64.so.7", mode=os.RTLD_NOLOAD | os.RTLD_GLOBAL)
         except OSError:
             _HIP = ctypes.CDLL(str(Path(torch.__file__).parent / "lib" / "libamdhip64.so"), mode=os.RTLD_GLOBAL)
-        _HIP.hipHostRegister.restype = c_i32
-        _HIP.hipHostRegister.argtypes = [vp, ctypes.c_size_t, ctypes.c_uint]
-        _HIP.hipHostUnregister.restype = c_i32
-        _HIP.hipHostUnregister.argtypes = [vp]
+        _HIP.hipHostMalloc.restype = c_i32
+        _HIP.hipHostMalloc.argtypes = [ctypes.POINTER(vp), ctypes.c_size_t, ctypes.c_uint]
+        _HIP.hipHostFree.restype = c_i32
+        _HIP.hipHostFree.argtypes = [vp]
         _HIP.hipMemcpyAsync.restype = c_i32
         _HIP.hipMemcpyAsync.argtypes = [vp, vp, ctypes.c_size_t, c_i32, vp]
         _HIP.hipHostGetDevicePointer.restype = c_i32
@@ -160,7 +161,7 @@ def hip_runtime():
 
 def device_address(t: torch.Tensor) -> int:
     """Address of ``t``'s first element as the GPU sees it: HBM tensors as they are, page-locked
-    host memory (torch-pinned or hipHostRegister'ed) through its device mapping."""
+    host memory (torch-pinned or hipHostMalloc'ed) through its device mapping."""
     if t.is_cuda:
         return t.data_ptr()
     out = vp()
@@ -173,9 +174,8 @@ HIP_MEMCPY_H2D, HIP_MEMCPY_D2H = 1, 2
 
 
 def memcpy_async(dst: torch.Tensor, src: torch.Tensor, stream) -> None:
-    """Raw DMA copy between a device tensor and a registered (page-locked) host tensor on
-    ``stream`` (a torch stream).  torch does not know hipHostRegister'ed memory is pinned and
-    would stage such copies through a bounce buffer."""
+    """Raw DMA copy between a device tensor and a page-locked host tensor (a PinnedHostBuffer's)
+    on ``stream`` (a torch stream), without going through torch's own pinned-memory bookkeeping."""
     n = src.numel() * src.element_size()
     assert dst.numel() * dst.element_size() == n
     if n == 0:
@@ -188,23 +188,42 @@ def memcpy_async(dst: torch.Tensor, src: torch.Tensor, stream) -> None:
 PREFAULT_MIN_BYTES = 64 << 20
 
 
+def _host_free(p: int) -> None:
+    try:
+        hip_runtime().hipHostFree(ctypes.c_void_p(p))
+    except Exception:  # noqa: BLE001
+        pass
+
+
 class PinnedHostBuffer:
-    """Exact-size page-locked host memory: a plain CPU tensor registered with hipHostRegister
-    (torch's pinned allocator rounds requests up to a power of two, which for 100 GB spill
-    buffers would double the host footprint)."""
+    """Exact-size page-locked host memory: allocated pinned with hipHostMalloc and wrapped as a
+    CPU tensor (torch's pinned allocator rounds requests up to a power of two, which for 100 GB
+    spill buffers would double the host footprint; page-locking memory the process already owns
+    with hipHostRegister is refused by some hosts).  The pages are freed when the last tensor
+    view of them is gone."""
 
     def __init__(self, shape, dtype=torch.uint8, prefault: bool = False):
-        self.tensor = torch.empty(shape, dtype=dtype)
-        nbytes = self.tensor.numel() * self.tensor.element_size()
-        self.registered = False
+        if isinstance(shape, int):
+            shape = (shape,)
+        n = 1
+        for d in shape:
+            n *= d
+        nbytes = n * torch.empty(0, dtype=dtype).element_size()
+        self.registered = False        # page-locked memory held
         self.pending = None            # event after the last queued copy of the last lease
-        if prefault and nbytes >= PREFAULT_MIN_BYTES:
-            # first touch by torch's CPU threads before hipHostRegister; measured no faster on the
-            # box (~15 GB/s of fresh pages either way, profiles/r6/r6f_pinned.log), so off by default
-            self.tensor.view(-1).view(torch.uint8).zero_()
         if nbytes:
-            check(hip_runtime().hipHostRegister(ctypes.c_void_p(self.tensor.data_ptr()), nbytes, 0), "hipHostRegister")
+            p = vp()
+            check(hip_runtime().hipHostMalloc(ctypes.byref(p), nbytes, 0), "hipHostMalloc")
+            mem = (ctypes.c_uint8 * nbytes).from_address(p.value)
+            weakref.finalize(mem, _host_free, p.value)      # torch's storage keeps ``mem`` alive
+            self.tensor = torch.frombuffer(mem, dtype=torch.uint8).view(dtype).view(*shape)
             self.registered = True
+        else:
+            self.tensor = torch.empty(shape, dtype=dtype)
+        if prefault and nbytes >= PREFAULT_MIN_BYTES:
+            # first touch by torch's CPU threads; measured no faster (~15 GB/s of fresh pages
+            # either way), so off by default
+            self.tensor.view(-1).view(torch.uint8).zero_()
 
     def wait(self):
         """Block until the copies queued on the buffer by its last lease are done."""
@@ -220,7 +239,6 @@ class PinnedHostBuffer:
                 self.wait()
             elif torch.cuda.is_available() and torch.cuda.is_initialized():
                 torch.cuda.synchronize()
-            hip_runtime().hipHostUnregister(ctypes.c_void_p(self.tensor.data_ptr()))
             self.registered = False
         self.tensor = None
 

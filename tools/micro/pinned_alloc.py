@@ -1,6 +1,7 @@
-"""Page-locking cost of fresh host memory: hipHostRegister of a malloc'd buffer (untouched, or
-first touched in parallel by torch's CPU threads: ops/_lib.PinnedHostBuffer prefault) vs
-hipHostMalloc (driver-allocated page-locked memory) vs torch's pinned allocator."""
+"""Cost of fresh page-locked host memory: ops/_lib.PinnedHostBuffer (hipHostMalloc wrapped as a
+tensor; with prefault also touched by torch's CPU threads) vs raw hipHostMalloc with flag
+variants vs torch's pinned allocator.  (The hipHostRegister numbers in the logs under profiles/
+are from when PinnedHostBuffer page-locked a malloc'd buffer.)"""
 import ctypes
 import sys
 import time
@@ -22,7 +23,7 @@ for gb in (2, 8, 8):
         t0 = time.perf_counter()
         b = _lib.PinnedHostBuffer((nb,), prefault=pre)
         dt = time.perf_counter() - t0
-        print(f"{gb} GB register prefault={pre}: {dt:.3f} s ({gb / dt:.1f} GB/s)", flush=True)
+        print(f"{gb} GB PinnedHostBuffer prefault={pre}: {dt:.3f} s ({gb / dt:.1f} GB/s)", flush=True)
         b.release()
         del b
     for flags in (0, 0x4):                    # default, hipHostMallocNumaUser? (flag variants)
