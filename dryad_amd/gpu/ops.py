@@ -10,7 +10,8 @@ Hot paths are HIP kernels: key normalisation (dr_build_keys / dr_extract_keys), 
 (dr_sort_u128), hashing and partition passes (dr_hash_dest / dr_partition_pass_u128), range
 destinations (dr_range_dest_u128), segmented reductions (dr_seg_reduce), merge-join expansion
 (dr_join_ranges / dr_join_emit), the hash join (dr_hj_*), whole-partition aggregates
-(dr_reduce_multi), row gathers (dr_gather_rows) and the synthetic TeraSort store.
+(dr_reduce_multi), row gathers (dr_gather_rows), the string-key sort and range destinations
+(dr_str_*, ops/strsort.py) and the synthetic TeraSort store.
 Elementwise projections/predicates are traced user lambdas executed as PyTorch-ROCm tensor ops.
 """
 from __future__ import annotations
@@ -23,6 +24,7 @@ from ..compiler.decomposition import Sym, substitute
 from ..ops import recordsort as RS
 from ..ops import relational as R
 from ..ops import sort as S
+from ..ops import strsort as SS
 from . import stats
 from . import trace as TR
 from .table import DeviceTable, PartialMeta, Ported, PortTables, Shape, from_objects
@@ -154,6 +156,59 @@ def eq_key_entries(table: DeviceTable, key_fn, comparer=None):
         return e, b0, lo_mask, skeys, (packed, tuple(str(c.dtype) for c in cols))
     e, b0, lo_mask = R.build_keys(cols)
     return e, b0, lo_mask, skeys, None
+
+
+def string_key(table: DeviceTable, key_fn, comparer=None):
+    """(heap, off, len) of an ordering key that is one string (TR.string_key), else None: the
+    device string sort and range partition (ops/strsort.py) order it exactly like the object
+    path's default comparison.  A custom comparer stays on the host."""
+    if comparer is not None or not isinstance(table, DeviceTable):
+        return None
+    s = TR.string_key(key_fn, table)
+    if s is None:
+        return None
+    _row_index_fits(table.n)
+    return s.heap, s.off, s.len
+
+
+def _str_keys_table(t):
+    """A sample / separator table of string keys: a text table of plain strings (an entry table
+    has ``lo`` / ``hi`` columns and no heap), else None."""
+    if isinstance(t, DeviceTable) and t.heap is not None and t.shape.kind == "text" and t.shape.pytype is str:
+        return t
+    return None
+
+
+def _str_keys(heap, off, ln, idx) -> DeviceTable:
+    """Strings idx[0], idx[1], ... of (heap, off, len) as a text table of plain strings over a
+    compact heap of its own (samples and separators travel between vertices)."""
+    from ..ops.channel import compact_heap
+    from .table import text_table
+    ln = ln.to(torch.int64).index_select(0, idx)
+    nheap, noff = compact_heap(heap, off.index_select(0, idx), ln)
+    return text_table(nheap, noff, ln, str)
+
+
+def _host_str_keys(seps: list, device):
+    """User range separators of Python ``str`` as a small (heap, off, len) on the device."""
+    from .table import _encode_strings
+    if len(seps) > SS.MAX_SEPARATORS:
+        raise NotTraceable("more than 255 range separators")
+    if any(not isinstance(x, str) for x in seps):
+        raise NotTraceable("separators of a string key that are not strings")
+    heap, off, ln = _encode_strings(seps)
+    return heap.to(device), off.to(device), ln.to(device)
+
+
+def _partition_by_dest(t: DeviceTable, dest: torch.Tensor, n: int, v):
+    """Ported copy of ``t`` with row i in port dest[i] (int32, < n <= 256), stable within a port:
+    ``dest`` stands where range_dest puts an entry's destination."""
+    out = partition_by_entries(t, dest.to(torch.uint8), n, v.world.size, _dest_place(v))
+    if out is not None:
+        return out
+    e = torch.stack([torch.arange(t.n, dtype=torch.int64, device=t.device), dest.to(torch.int64)], 1).contiguous()
+    part, starts = S.partition_pass(e, 64)
+    return Ported(t.take(_perm(part)), starts[: n + 1].tolist())
 
 
 def _perm(entries: torch.Tensor) -> torch.Tensor:
@@ -513,6 +568,9 @@ def op_sort(op, inputs, v):
     t = _check(_one(inputs))
     if t.n <= 1:
         return t
+    sk = string_key(t, op["key"], op.get("comparer"))
+    if sk is not None:
+        return t.take(SS.sort_strings(*sk, descending=op.get("descending", False)))
     bs = _pooled_set(t, v)
     if bs is not None and bs.layout == "pitch128":
         # records at a 128-byte pitch (op_read of a one-rank gen://terasort -> OrderBy stage)
@@ -668,11 +726,15 @@ def op_hash_partition(op, inputs, v):
 
 def op_sample(op, inputs, v):
     t = _check(_one(inputs))
-    e, b0, lo_mask = key_entries(t, op["key"], op.get("comparer"), False)
     n = t.n
     rate = op.get("rate", 0.001)
     m = n if n * rate < 10 else max(1, int(n * rate))
     stride = max(1, n // max(m, 1))
+    sk = string_key(t, op["key"], op.get("comparer"))
+    if sk is not None:
+        # the sampled key strings as a text table with a heap of its own (see _str_keys_table)
+        return _str_keys(*sk, torch.arange(0, n, stride, device=t.device)[:m])
+    e, b0, lo_mask = key_entries(t, op["key"], op.get("comparer"), False)
     samp = e[::stride][:m].clone() if n else e
     samp[:, 0] &= RS._as_i64(lo_mask)
     return DeviceTable.from_columns({"lo": samp[:, 0].contiguous(), "hi": samp[:, 1].contiguous()}, E_SHAPE)
@@ -687,8 +749,17 @@ def _entries_table(t):
 
 
 def op_separators(op, inputs, v):
-    t = _entries_table(_check(_one(inputs)))
+    t = _check(_one(inputs))
     n = op["count"]
+    if _str_keys_table(t) is not None:
+        # sampled string keys: sorted in the partition order, the same positions picked
+        if op.get("comparer") is not None:
+            raise NotTraceable("custom comparer")
+        heap, off, ln = t.heap, t.cols["off"], t.cols["len"]
+        perm = SS.sort_strings(heap, off, ln, descending=op.get("descending", False))
+        pos = torch.tensor([(j * t.n) // n for j in range(1, n)] if t.n else [], dtype=torch.int64, device=perm.device)
+        return _str_keys(heap, off, ln, perm.index_select(0, pos))
+    t = _entries_table(t)
     if t.n == 0:
         return DeviceTable.from_columns({"lo": torch.empty(0, dtype=torch.int64, device=v.device),
                                          "hi": torch.empty(0, dtype=torch.int64, device=v.device)}, E_SHAPE)
@@ -731,6 +802,20 @@ def op_range_partition(op, inputs, v):
     seps_t = inputs[1] if len(inputs) > 1 else None
     if t.n == 0:
         return Ported(t, [0] * (n + 1))
+    sk = string_key(t, op["key"], op.get("comparer"))
+    if sk is not None:
+        if n > 256:
+            raise NotTraceable("more than 256 range partitions of a string key")
+        if op.get("separators") is not None:
+            seps = _host_str_keys(list(op["separators"]), t.device)
+        elif seps_t is None or seps_t.n == 0:
+            return Ported(t, [0] + [t.n] * n)
+        elif _str_keys_table(seps_t) is None:
+            raise NotTraceable("separators of a string key are not a table of strings")
+        else:
+            seps = (seps_t.heap, seps_t.cols["off"], seps_t.cols["len"])
+        dest = SS.range_dest_strings(*sk, *seps, descending=op.get("descending", False), count=n)
+        return _partition_by_dest(t, dest, n, v)
     e, _, lo_mask = key_entries(t, op["key"], op.get("comparer"), False)
     if op.get("separators") is not None:
         seps = _separator_entries(t, op["key"], list(op["separators"]))

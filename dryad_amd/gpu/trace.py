@@ -384,6 +384,31 @@ def to_mask(res, table: DeviceTable) -> torch.Tensor:
     raise NotTraceable("predicate did not produce a boolean field")
 
 
+def string_key(key_fn, table: DeviceTable):
+    """The StrCol an ordering key selector picks, or None when the key is not one string:
+    a string field of a record table (``lambda r: r.name``, ``lambda r: r[1]``), or the identity
+    over a table of plain strings (``lambda s: s``: the selector gets a StrCol over the table's
+    heap and must hand that very object back).  Composite keys with a string part and LineRecord
+    tables stay with key_columns / proxy, which refuse them."""
+    if table.n == 0:
+        return None
+    if table.heap is not None:
+        if table.shape.kind != "text" or table.shape.pytype is not str or uses_identity(key_fn):
+            return None
+        s = StrCol(table.heap, table.cols["off"], table.cols["len"])
+        try:
+            return s if key_fn(s) is s else None
+        except (NotTraceable, TypeError, AttributeError, RuntimeError):
+            return None
+    if not table.strs:
+        return None
+    try:
+        res = call(key_fn, table)
+    except NotTraceable:
+        return None
+    return res if isinstance(res, StrCol) else None
+
+
 def key_columns(res, table: DeviceTable):
     """Key selector result -> ("bytes", ByteField) | ("cols", [tensors])."""
     if isinstance(res, ByteField):
