@@ -832,6 +832,345 @@ __global__ __launch_bounds__(64) void kmeans_rerank_kernel(const float* __restri
   }
 }
 
+// ---------------------------------------------------------------------------------------------
+// 64 < K <= 1024 on the bf16 plane: points stationary in registers, centroids streamed through LDS
+// in 64-centroid chunks (dr_kmeans_step_plane).
+//
+// kmeans_cprep_kernel writes the split centroids once per step in the exact byte image of an LDS
+// chunk: [ch 64 x kCRow bf16][cm 64 x kCRow bf16][cnorm 64 f32], rows past K zero with cnorm = +inf,
+// followed after the last chunk by cmax = sqrt(max cnorm).  Staging a chunk is then a straight
+// 16-byte-per-lane copy (590 KB at K = 1024: L2-resident).
+constexpr int kLkChunkBytes = 2 * 64 * kCRow * 2 + 64 * 4;   // 37120
+constexpr int kLkUnits = kLkChunkBytes / 16;                 // 16-byte units per chunk
+constexpr int kLkQuarter = kLkUnits / 4;                     // staged per 16-centroid sub-tile
+static_assert(kLkUnits % 4 == 0, "chunk image splits into four equal copies");
+static_assert(kLkChunkBytes % 16 == 0 && (kCRow * 2) % 16 == 0, "chunk image must be b128-copyable");
+
+__global__ __launch_bounds__(256) void kmeans_cprep_kernel(const float* __restrict__ C,
+                                                           const float* __restrict__ cnorm, int K,
+                                                           unsigned char* __restrict__ cws) {
+  __shared__ float wmax[4];
+  const int j = blockIdx.x, t = threadIdx.x;
+  __bf16* chi = reinterpret_cast<__bf16*>(cws + (size_t)j * kLkChunkBytes);
+  __bf16* cmd = chi + 64 * kCRow;
+  float* cn = reinterpret_cast<float*>(cmd + 64 * kCRow);
+  for (int i = t; i < 64 * kCRow; i += 256) {
+    const int c = 64 * j + i / kCRow, d = i % kCRow;
+    const float v = (c < K && d < D) ? C[(uint64_t)c * D + d] : 0.f;
+    const __bf16 vh = (__bf16)v;
+    chi[i] = vh;
+    cmd[i] = (__bf16)(v - (float)vh);
+  }
+  if (t < 64) cn[t] = 64 * j + t < K ? cnorm[64 * j + t] : __builtin_inff();
+  if (j == 0) {
+    float m = 0.f;
+    for (int c = t; c < K; c += 256) m = fmaxf(m, cnorm[c]);
+#pragma unroll
+    for (int x = 32; x >= 1; x >>= 1) m = fmaxf(m, __shfl_xor(m, x, 64));
+    if ((t & 63) == 0) wmax[t >> 6] = m;
+    __syncthreads();
+    if (t == 0)
+      *reinterpret_cast<float*>(cws + (size_t)gridDim.x * kLkChunkBytes) =
+          sqrtf(fmaxf(fmaxf(wmax[0], wmax[1]), fmaxf(wmax[2], wmax[3])));
+  }
+}
+
+// Assignment.  A workgroup of W waves owns a block of 16 T W points: every wave keeps T 16-point
+// tiles of the plane in registers (lane (r, g): dims 32 s + 8 g .. + 7 of point r, the B operand
+// of the 16x16x32 bf16 MFMA) and the workgroup walks the ceil(K / 64) centroid chunks.  Per
+// 16-centroid sub-tile and 32-dim slice the ah / am fragments are read from LDS once and feed
+// 2 T MFMAs, so T is the reuse factor of every LDS byte and of every centroid byte fetched from L2.
+// The chunks are double-buffered: chunk j + 1 is fetched into registers before chunk j's MFMAs and
+// stored to the other LDS buffer after them, one barrier per chunk; the chunk sequence runs on
+// across point blocks (all blocks see the same centroids), so the pipeline never drains.  Best,
+// runner-up and index are carried per lane over all chunks and merged over the 4 lanes of a point
+// once per block.  The next block's tiles are requested at the top of a block and land under its
+// MFMAs (registers: 16 T points + 16 T prefetch + 4 T accumulators; two waves per SIMD).
+template <int T, int W>
+__global__ __launch_bounds__(64 * W) void kmeans_assign_tiled_kernel(const __bf16* __restrict__ XH,
+                                                                     const float* __restrict__ xnorm, uint64_t n,
+                                                                     const uint4* __restrict__ cws,
+                                                                     const float* __restrict__ cmax_p, int K,
+                                                                     int32_t* __restrict__ assign) {
+  constexpr int NT = 64 * W;
+  constexpr int NQ = (kLkQuarter + NT - 1) / NT;
+  constexpr uint64_t PB = 16 * T * W;
+  __shared__ uint4 cbuf[2 * kLkUnits];
+  const int t = threadIdx.x, w = t >> 6, l = t & 63, r = l & 15, g = l >> 4;
+  const int nch = (K + 63) / 64;
+  for (int i = t; i < kLkUnits; i += NT) cbuf[i] = cws[i];
+  const float cmax = *cmax_p;
+  __syncthreads();
+  struct Pts {
+    bf16x8 x[4];
+    float xn;
+  };
+  const uint64_t blocks = (n + PB - 1) / PB;
+  // clamped rows: a point past n re-reads point n - 1 and stores nothing
+  auto load = [&](uint64_t blk, Pts* d) {
+#pragma unroll
+    for (int tt = 0; tt < T; ++tt) {
+      const uint64_t p = min(blk * PB + (uint64_t)((w * T + tt) * 16 + r), n - 1);
+#pragma unroll
+      for (int s_ = 0; s_ < 4; ++s_) d[tt].x[s_] = *reinterpret_cast<const bf16x8*>(XH + p * D + 32 * s_ + 8 * g);
+      d[tt].xn = xnorm[p];
+    }
+  };
+  Pts cur[T], nxt[T];
+  if ((uint64_t)blockIdx.x < blocks) load(blockIdx.x, cur);
+  int par = 0;
+  for (uint64_t blk = blockIdx.x; blk < blocks; blk += gridDim.x) {
+    const uint64_t nb = blk + gridDim.x;
+    load(nb < blocks ? nb : blk, nxt);
+    float bd[T], sd[T];
+    int bj[T];
+#pragma unroll
+    for (int tt = 0; tt < T; ++tt) {
+      bd[tt] = __builtin_inff();
+      sd[tt] = __builtin_inff();
+      bj[tt] = 0;
+    }
+#pragma unroll 1
+    for (int j = 0; j < nch; ++j, par ^= 1) {
+      const int jn = j + 1 < nch ? j + 1 : 0;
+      const uint4* src = cws + (size_t)jn * kLkUnits;
+      uint4* dst = cbuf + (par ^ 1) * kLkUnits;
+      const __bf16* chi = reinterpret_cast<const __bf16*>(cbuf + par * kLkUnits);
+      const __bf16* cmd = chi + 64 * kCRow;
+      const float* cn = reinterpret_cast<const float*>(cmd + 64 * kCRow);
+#pragma unroll 1
+      for (int ct = 0; ct < 4; ++ct) {
+        // a quarter of the next chunk is in flight under each sub-tile's MFMAs
+        uint4 st[NQ];
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) st[q] = src[ct * kLkQuarter + min(t + NT * q, kLkQuarter - 1)];
+        f32x4 Dt[T];
+#pragma unroll
+        for (int tt = 0; tt < T; ++tt) Dt[tt] = f32x4{};
+#pragma unroll
+        for (int s_ = 0; s_ < 4; ++s_) {
+          const bf16x8 ah = *reinterpret_cast<const bf16x8*>(chi + (ct * 16 + r) * kCRow + 32 * s_ + 8 * g);
+          const bf16x8 am = *reinterpret_cast<const bf16x8*>(cmd + (ct * 16 + r) * kCRow + 32 * s_ + 8 * g);
+#pragma unroll
+          for (int tt = 0; tt < T; ++tt) {
+            Dt[tt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah, cur[tt].x[s_], Dt[tt], 0, 0, 0);
+            Dt[tt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(am, cur[tt].x[s_], Dt[tt], 0, 0, 0);
+          }
+        }
+        const float4 cv = *reinterpret_cast<const float4*>(cn + ct * 16 + 4 * g);
+        const float cc[4] = {cv.x, cv.y, cv.z, cv.w};
+#pragma unroll
+        for (int tt = 0; tt < T; ++tt)
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            const int c = 64 * j + ct * 16 + 4 * g + q;
+            const float d = fmaf(-2.f, Dt[tt][q], cc[q]);
+            sd[tt] = fminf(sd[tt], fmaxf(bd[tt], d));
+            bj[tt] = d < bd[tt] ? c : bj[tt];
+            bd[tt] = fminf(bd[tt], d);
+          }
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) {
+          const int i = t + NT * q;
+          if (i < kLkQuarter) dst[ct * kLkQuarter + i] = st[q];
+        }
+      }
+      __syncthreads();
+    }
+#pragma unroll
+    for (int tt = 0; tt < T; ++tt) {
+      float b = bd[tt], s2 = sd[tt];
+      int bi = bj[tt];
+#pragma unroll
+      for (int m = 16; m <= 32; m <<= 1) {
+        const float obd = __shfl_xor(b, m, 64), osd = __shfl_xor(s2, m, 64);
+        const int obj = __shfl_xor(bi, m, 64);
+        if (obd < b || (obd == b && obj < bi)) {
+          s2 = fminf(b, osd);
+          b = obd;
+          bi = obj;
+        } else {
+          s2 = fminf(s2, obd);
+        }
+      }
+      const uint64_t p = blk * PB + (uint64_t)((w * T + tt) * 16 + r);
+      const bool near = K > 1 && (s2 - b) <= 2.f * kKmTolH * cur[tt].xn * cmax;
+      if (g == 0 && p < n) assign[p] = near ? (int32_t)((uint32_t)bi | 0x80000000u) : bi;
+    }
+#pragma unroll
+    for (int tt = 0; tt < T; ++tt) cur[tt] = nxt[tt];
+  }
+}
+
+// Exact f32 re-rank for any K (the K <= 64 kernel above ranks one centroid per lane): one wave per
+// P listed points, lane l scans centroids l, l + 64, ... with the same two-accumulator fma order
+// and keeps its best (lowest index on ties), then the same butterfly.  A centroid row fetched by a
+// lane serves P points.  Corrects assign only: the plane path keeps its sums by kmeans_movers.
+template <int P>
+__global__ __launch_bounds__(64) void kmeans_rerank_strided_kernel(const float* __restrict__ X,
+                                                                   const float* __restrict__ C,
+                                                                   const float* __restrict__ cnorm, int K,
+                                                                   const uint32_t* __restrict__ near_cnt,
+                                                                   const uint32_t* __restrict__ near_list,
+                                                                   int32_t* __restrict__ assign, uint64_t n) {
+  const uint32_t total = (uint64_t)*near_cnt < n ? *near_cnt : (uint32_t)n;
+  const int l = threadIdx.x;
+  for (uint64_t i0 = (uint64_t)blockIdx.x * P; i0 < total; i0 += (uint64_t)gridDim.x * P) {
+    uint64_t p[P];
+    int est[P], bj[P];
+    float d[P];
+    const float4* xr[P];
+#pragma unroll
+    for (int u = 0; u < P; ++u) {
+      // a short last group repeats its last entry (the same value is stored twice)
+      const uint64_t i = i0 + u < total ? i0 + u : total - 1;
+      p[u] = near_list[2 * i];
+      est[u] = (int)near_list[2 * i + 1];
+      xr[u] = reinterpret_cast<const float4*>(X + p[u] * D);
+      d[u] = __builtin_inff();
+      bj[u] = l;
+    }
+    for (int c = l; c < K; c += 64) {
+      const float4* cr = reinterpret_cast<const float4*>(C + (uint64_t)c * D);
+      float a0[P], a1[P];
+#pragma unroll
+      for (int u = 0; u < P; ++u) a0[u] = a1[u] = 0.f;
+      for (int k = 0; k < D / 4; k += 2) {
+        const float4 c0 = cr[k], c1 = cr[k + 1];
+#pragma unroll
+        for (int u = 0; u < P; ++u) {
+          const float4 x0 = xr[u][k], x1 = xr[u][k + 1];
+          a0[u] = fmaf(x0.x, c0.x, fmaf(x0.y, c0.y, fmaf(x0.z, c0.z, fmaf(x0.w, c0.w, a0[u]))));
+          a1[u] = fmaf(x1.x, c1.x, fmaf(x1.y, c1.y, fmaf(x1.z, c1.z, fmaf(x1.w, c1.w, a1[u]))));
+        }
+      }
+      const float cnc = cnorm[c];
+#pragma unroll
+      for (int u = 0; u < P; ++u) {
+        const float dc = cnc - 2.f * (a0[u] + a1[u]);
+        if (dc < d[u]) { d[u] = dc; bj[u] = c; }
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < P; ++u) {
+      float du = d[u];
+      int bu = bj[u];
+#pragma unroll
+      for (int m = 32; m >= 1; m >>= 1) {
+        const float od = __shfl_xor(du, m, 64);
+        const int oj = __shfl_xor(bu, m, 64);
+        if (od < du || (od == du && oj < bu)) { du = od; bu = oj; }
+      }
+      if (l == 0 && bu != est[u]) assign[p[u]] = bu;
+    }
+  }
+}
+
+// Movers for K > 64, where an f64 [K][128] slab no longer fits LDS: grid (blocks, 128 / SW), a
+// workgroup keeps the f64 [K][SW] slab of dimension slice blockIdx.y.  A slab row belongs to one
+// wave (row & 3) and, when a row is narrower than a wave, to one of its 64 / SW lane groups
+// ((row >> 2) % G), so every update is a plain f64 read-modify-write by the lanes that own those
+// words: G rows per wave instruction, a lane per dimension.  Each lane group walks its own ballot
+// of the 64-point sub-batch.  prev is only read here (the slices of a batch run concurrently);
+// kmeans_copy_assign brings it up to date afterwards.  Slice 0 keeps the counts.
+template <int SW>
+__global__ __launch_bounds__(256) void kmeans_movers_sliced_kernel(const float* __restrict__ X, uint64_t n,
+                                                                   const int32_t* __restrict__ assign,
+                                                                   const int32_t* __restrict__ prev, int K,
+                                                                   double* __restrict__ S, long long* __restrict__ cnt) {
+  extern __shared__ __attribute__((aligned(16))) double mslab[];   // [K][SW]
+  int* dcnt = reinterpret_cast<int*>(mslab + (size_t)K * SW);      // [K]
+  int* cur_s = dcnt + K;                                           // [256]
+  int* old_s = cur_s + 256;                                        // [256]
+  constexpr int LW = SW < 64 ? SW : 64;   // lanes per row
+  constexpr int G = 64 / LW;              // rows per wave instruction
+  constexpr int NV = SW / LW;             // dims per lane
+  constexpr int U = 8;                    // rows in flight per lane group
+  const int t = threadIdx.x, w = t >> 6, l = t & 63, gi = l / LW, dl = l % LW;
+  const int d0 = blockIdx.y * SW;
+  for (int i = t; i < K * SW; i += 256) mslab[i] = 0.0;
+  for (int i = t; i < K; i += 256) dcnt[i] = 0;
+  for (uint64_t b = (uint64_t)blockIdx.x * 256; b < n; b += (uint64_t)gridDim.x * 256) {
+    const uint64_t p = b + t;
+    int a = -1, o = -1;
+    if (p < n) {
+      a = assign[p];
+      o = prev[p];
+    }
+    __syncthreads();   // the previous batch's readers are done with cur_s / old_s (and the zeroing)
+    cur_s[t] = a;
+    old_s[t] = o;
+    __syncthreads();
+#pragma unroll 1
+    for (int c = 0; c < 4; ++c) {
+      const int ca = cur_s[64 * c + l], co = old_s[64 * c + l];
+      const bool mv = ca != co;
+      uint64_t madd = 0, msub = 0;
+#pragma unroll
+      for (int own = 0; own < G; ++own) {
+        const uint64_t ma = ballot64(mv && ca >= 0 && (ca & 3) == w && ((ca >> 2) % G) == own);
+        const uint64_t ms = ballot64(mv && co >= 0 && (co & 3) == w && ((co >> 2) % G) == own);
+        if (gi == own) {
+          madd = ma;
+          msub = ms;
+        }
+      }
+      while (__any((madd | msub) != 0)) {
+        int idx[U], row[U];
+        double sgn[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+          idx[u] = 0;
+          row[u] = -1;
+          sgn[u] = 0.0;
+          if (madd) {
+            idx[u] = __builtin_ctzll(madd);
+            madd &= madd - 1;
+            row[u] = cur_s[64 * c + idx[u]];
+            sgn[u] = 1.0;
+          } else if (msub) {
+            idx[u] = __builtin_ctzll(msub);
+            msub &= msub - 1;
+            row[u] = old_s[64 * c + idx[u]];
+            sgn[u] = -1.0;
+          }
+        }
+        float v[U][NV];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+          // idx = 0 is in range whenever any entry of this sub-batch is (b + 64 c < n)
+          const float* xr = X + (b + 64 * c + idx[u]) * D + d0 + dl;
+#pragma unroll
+          for (int e = 0; e < NV; ++e) v[u][e] = row[u] >= 0 ? xr[64 * e] : 0.f;
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+          if (row[u] >= 0) {
+            double* dst = mslab + (size_t)row[u] * SW + dl;
+#pragma unroll
+            for (int e = 0; e < NV; ++e) dst[64 * e] += sgn[u] * (double)v[u][e];
+            if (blockIdx.y == 0 && dl == 0) dcnt[row[u]] += sgn[u] > 0 ? 1 : -1;
+          }
+        }
+      }
+    }
+  }
+  __syncthreads();
+  for (int i = t; i < K * SW; i += 256) {
+    const double v = mslab[i];
+    if (v != 0.0) atomicAdd(S + (uint64_t)(i / SW) * D + d0 + (i % SW), v);
+  }
+  if (blockIdx.y == 0)
+    for (int i = t; i < K; i += 256)
+      if (dcnt[i]) atomicAdd(reinterpret_cast<unsigned long long*>(cnt + i), (unsigned long long)(long long)dcnt[i]);
+}
+
+__global__ __launch_bounds__(256) void kmeans_copy_assign(const int32_t* __restrict__ assign, uint64_t n,
+                                                          int32_t* __restrict__ prev) {
+  for (uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; p < n; p += (uint64_t)gridDim.x * blockDim.x)
+    prev[p] = assign[p];
+}
+
 uint32_t step_smem(int K, bool cres, bool slab) {
   const int Kc = cres ? ((K + CT - 1) / CT) * CT : CT;
   return (uint32_t)((Kc * LDW + Kc + 2 * kPts) * 4 + (slab ? (uint32_t)K * D * 4 + (uint32_t)K * 4 : 0));
@@ -979,6 +1318,58 @@ DR_API int dr_kmeans_step_hi(const __bf16* XH, const float* xnorm, const float* 
   const uint64_t mb = (n + 255) / 256;
   const uint64_t mcap = 4 * (uint64_t)num_cus();
   kmeans_movers_kernel<<<(unsigned)(mb < mcap ? mb : mcap), 256, 0, s>>>(X, n, assign, prev, K, S, cnt);
+  DR_LAUNCH_CHECK();
+  return 0;
+}
+
+// Bytes of the split-centroid workspace of dr_kmeans_step_plane for K clusters.
+DR_API uint64_t dr_kmeans_centroid_workspace(int K) {
+  return (uint64_t)((K < 1 ? 1 : K) + 63) / 64 * kLkChunkBytes + 16;
+}
+
+// dr_kmeans_step_hi for 1 <= K <= 1024: K <= 64 is that call unchanged; above it the centroids are
+// split once into cws (dr_kmeans_centroid_workspace(K) bytes) and streamed by the K-tiled kernel.
+DR_API int dr_kmeans_step_plane(const __bf16* XH, const float* xnorm, const float* X, uint64_t n, const float* C,
+                                int K, float* cnorm_ws, int32_t* assign, int32_t* prev, double* S, long long* cnt,
+                                void* near_ws, void* cws, hipStream_t s) {
+  if (K <= 64) return dr_kmeans_step_hi(XH, xnorm, X, n, C, K, cnorm_ws, assign, prev, S, cnt, near_ws, s);
+  if (K > 1024 || !assign || !prev || !S || !cnt || !near_ws || !cws) return (int)hipErrorInvalidValue;
+  sq_norms_kernel<<<K, 64, 0, s>>>(C, K, cnorm_ws);
+  if (n == 0) return 0;
+  constexpr int T = 4, W = 8;
+  const int nch = (K + 63) / 64;
+  unsigned char* cwb = reinterpret_cast<unsigned char*>(cws);
+  kmeans_cprep_kernel<<<nch, 256, 0, s>>>(C, cnorm_ws, K, cwb);
+  uint32_t* near_cnt = reinterpret_cast<uint32_t*>(near_ws);
+  uint32_t* near_list = near_cnt + 4;
+  kmeans_near_reset<<<1, 64, 0, s>>>(near_cnt);
+  static int per_cu = 0;   // resident workgroups per CU (registers and the 2 x 36 KB chunk buffers)
+  if (per_cu == 0) {
+    hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kmeans_assign_tiled_kernel<T, W>, 64 * W, 0);
+    if (per_cu < 1) per_cu = 1;
+  }
+  const uint64_t blocks = (n + 16 * T * W - 1) / (16 * T * W);
+  const uint64_t cap = (uint64_t)per_cu * num_cus();
+  kmeans_assign_tiled_kernel<T, W><<<(unsigned)(blocks < cap ? blocks : cap), 64 * W, 0, s>>>(
+      XH, xnorm, n, reinterpret_cast<const uint4*>(cwb), reinterpret_cast<const float*>(cwb + (size_t)nch * kLkChunkBytes),
+      K, assign);
+  kmeans_near_list<<<grid_for(n, 256, 4096), 256, 0, s>>>(assign, n, near_cnt, near_list);
+  kmeans_rerank_strided_kernel<4><<<8192, 64, 0, s>>>(X, C, cnorm_ws, K, near_cnt, near_list, assign, n);
+  const uint64_t mb = (n + 255) / 256;
+#define DR_MOVERS(SWV)                                                                             \
+  do {                                                                                             \
+    const uint32_t sm = (uint32_t)K * SWV * 8 + (uint32_t)K * 4 + 2 * 256 * 4;                     \
+    const uint64_t mcap = (uint64_t)num_cus() * SWV / D > 0 ? (uint64_t)num_cus() * SWV / D : 1;   \
+    set_smem(kmeans_movers_sliced_kernel<SWV>, sm);                                                \
+    kmeans_movers_sliced_kernel<SWV><<<dim3((unsigned)(mb < mcap ? mb : mcap), D / SWV), 256, sm, s>>>( \
+        X, n, assign, prev, K, S, cnt);                                                            \
+  } while (0)
+  if (K <= 128) DR_MOVERS(128);
+  else if (K <= 256) DR_MOVERS(64);
+  else if (K <= 512) DR_MOVERS(32);
+  else DR_MOVERS(16);
+#undef DR_MOVERS
+  kmeans_copy_assign<<<grid_for(n, 256, 4096), 256, 0, s>>>(assign, n, prev);
   DR_LAUNCH_CHECK();
   return 0;
 }

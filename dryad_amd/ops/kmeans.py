@@ -1,11 +1,14 @@
 """k-means step on MFMA (HIP kernels in csrc/kernels/kmeans.hip).
 
-K <= 64 (the benchmark's K = 64) runs on a per-table state (``SplitPoints``, cached per point
-tensor): the bf16 rounding of every coordinate and |x| per point, written once, so an
-iteration's assignment kernel reads half the bytes of the f32 rows; and the per-cluster sums and
-counts, kept with the table and updated only for the points whose cluster changed (their exact
-f32 rows move from the old cluster's sums to the new one's).  Larger K, or a plane that does not
-fit in free HBM, use the f32 kernels.
+K <= 1024 runs on a per-table state (``SplitPoints``, cached per point tensor): the bf16 rounding
+of every coordinate and |x| per point, written once, so an iteration's assignment kernel reads
+half the bytes of the f32 rows; and the per-cluster sums and counts, kept with the table and
+updated only for the points whose cluster changed (their exact f32 rows move from the old
+cluster's sums to the new one's).  K <= 64 (the benchmark's K = 64) keeps all centroids in LDS;
+64 < K <= 1024 keeps the points in registers and streams the split centroids through LDS in
+64-centroid chunks (``dr_kmeans_step_plane``); ``step`` takes that path only on request
+(``planes=True``, see ``PLANES_DEFAULT_MAX_K``).  Larger K, or a plane that does not fit in free
+HBM, use the f32 kernels.
 """
 from __future__ import annotations
 
@@ -25,9 +28,17 @@ _lib.register_signatures({
     "dr_kmeans_gen": (c_i32, [vp, c_u64, c_i32, c_u64, c_i32, c_u64, vp]),
     "dr_kmeans_hi": (c_i32, [vp, c_u64, vp, vp, vp]),
     "dr_kmeans_step_hi": (c_i32, [vp, vp, vp, c_u64, vp, c_i32, vp, vp, vp, vp, vp, vp, vp]),
+    "dr_kmeans_centroid_workspace": (c_u64, [c_i32]),
+    "dr_kmeans_step_plane": (c_i32, [vp, vp, vp, c_u64, vp, c_i32, vp, vp, vp, vp, vp, vp, vp, vp]),
 })
 
-PLANES_MAX_K = 64
+PLANES_MAX_K = 1024
+# largest K that step() puts on the plane by itself (planes=None).  Above 64 the plane path is
+# opt-in (planes=True): its bf16 estimate cannot order centroids closer than ~8e-3 |x| max|c|, and
+# with several centroids per natural cluster every point is re-ranked in f32, which measured 5x
+# slower than the f32 kernels at K = 128 .. 1024 (profiles/kmeans_largek_bw.log); it wins only
+# when the centroids are that far apart.
+PLANES_DEFAULT_MAX_K = 64
 # free HBM kept beyond the planes (the step's workspace and whatever the job allocates next)
 PLANES_HEADROOM = 4 << 30
 
@@ -41,13 +52,16 @@ class KMeansWorkspace:
         self.assign = torch.empty(n, dtype=torch.int32, device=device)
         self.sums = torch.empty((k, DIM), dtype=torch.float64, device=device)
         self.counts = torch.empty(k, dtype=torch.int64, device=device)
-        # near-tie list of the K <= 64 bf16-MFMA path (count + (point, estimate) pairs)
-        self.near = torch.empty(int(_lib.lib().dr_kmeans_near_workspace(c_u64(n))) if k <= 64 else 16,
+        # near-tie list of the bf16-MFMA paths (count + (point, estimate) pairs)
+        self.near = torch.empty(int(_lib.lib().dr_kmeans_near_workspace(c_u64(n))) if k <= PLANES_MAX_K else 16,
                                 dtype=torch.uint8, device=device)
+        # split centroids (ch, cm, |c|^2 in 64-centroid chunks) of the 64 < K <= 1024 plane path
+        self.csplit = torch.empty(int(_lib.lib().dr_kmeans_centroid_workspace(k)) if 64 < k <= PLANES_MAX_K else 16,
+                                  dtype=torch.uint8, device=device)
 
 
 class SplitPoints:
-    """Per-point-table state of the K <= 64 path: ``xh`` [n, 128] bf16 (round-to-nearest of x),
+    """Per-point-table state of the plane path: ``xh`` [n, 128] bf16 (round-to-nearest of x),
     ``xnorm`` |x| per point, and the running per-cluster state of the last step: ``prev`` (final
     assignment, -1 = none), ``sums`` (K x 128 f64) and ``counts`` (K i64)."""
 
@@ -156,7 +170,7 @@ def step(points: torch.Tensor, centroids: torch.Tensor, ws: KMeansWorkspace | No
     ws.sums.zero_()
     ws.counts.zero_()
     sp = None
-    if planes is not False and 1 <= k <= PLANES_MAX_K and n > 0:
+    if planes is not False and 1 <= k <= (PLANES_MAX_K if planes else PLANES_DEFAULT_MAX_K) and n > 0:
         sp = split_points(points)
         if sp is None and planes:
             raise MemoryError(f"kmeans.step: the bf16 plane of {n} points ({split_bytes(n) >> 20} MiB) does not fit")
@@ -164,9 +178,9 @@ def step(points: torch.Tensor, centroids: torch.Tensor, ws: KMeansWorkspace | No
         raise ValueError(f"kmeans.step: the plane path needs 1 <= K <= {PLANES_MAX_K} (K = {k})")
     if sp is not None:
         sums, counts = sp.state_for(k)
-        _lib.call("dr_kmeans_step_hi", ptr(sp.xh), ptr(sp.xnorm), ptr(points), c_u64(n), ptr(centroids), k,
+        _lib.call("dr_kmeans_step_plane", ptr(sp.xh), ptr(sp.xnorm), ptr(points), c_u64(n), ptr(centroids), k,
                   ptr(ws.cnorm), ptr(ws.assign), ptr(sp.prev), ptr(sums), ptr(counts), ptr(ws.near),
-                  stream_of(points))
+                  ptr(ws.csplit), stream_of(points))
         ws.sums.copy_(sums)
         ws.counts.copy_(counts)
         return ws.sums, ws.counts, ws.assign[:n]
