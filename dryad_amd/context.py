@@ -137,6 +137,9 @@ _DEFAULTS = dict(
     #                               into the exchange's send rows (no input table; a benchmark variant)
     GroupByAggregation="auto",    # single-integer-key GroupBy: "auto" (radix aggregation for keys spanning
     #                               >= 2^32 values), "radix" or "sort" (ops/tuning.py)
+    TopKMinRows=1 << 24,          # OrderBy(...).Take(k) on the GPU: a partition of at least this many rows ...
+    TopKMaxFraction=1 / 8,        # ... with k <= rows * fraction selects its k smallest sort entries
+    #                               (ops/topk.py) instead of sorting every row (ops/tuning.py)
     ShuffleSlack=0.01,            # receive-buffer headroom of a range-partitioned exchange
     ExchangeOneRank=False,        # plan a one-partition OrderBy as the sampled range shuffle, so a one-rank
     #                               RCCL communicator (World.force_collectives) runs the multi-rank program

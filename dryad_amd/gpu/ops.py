@@ -11,7 +11,8 @@ Hot paths are HIP kernels: key normalisation (dr_build_keys / dr_extract_keys), 
 destinations (dr_range_dest_u128), segmented reductions (dr_seg_reduce), merge-join expansion
 (dr_join_ranges / dr_join_emit), the hash join (dr_hj_*), whole-partition aggregates
 (dr_reduce_multi), row gathers (dr_gather_rows), the string-key sort and range destinations
-(dr_str_*, ops/strsort.py) and the synthetic TeraSort store.
+(dr_str_*, ops/strsort.py), the radix select behind OrderBy + Take (dr_topk_*, ops/topk.py) and the
+synthetic TeraSort store.
 Elementwise projections/predicates are traced user lambdas executed as PyTorch-ROCm tensor ops.
 """
 from __future__ import annotations
@@ -597,6 +598,35 @@ def op_sort(op, inputs, v):
             return DeviceTable(out.shape[0], t.shape, rows=out)
     _, perm, _ = sort_perm(t, op["key"], op.get("comparer"), op.get("descending", False))
     return t.take(perm)
+
+
+def op_sort_take(sort_op, take_op, inputs, v):
+    """A ``sort`` op followed by a ``take`` op as one radix select (ops/topk.py): the entries of
+    the k first rows of the stable sort are selected and sorted, and only those k rows gathered.
+    Raises NotTraceable wherever the select does not serve, and the caller runs the two ops as
+    they are: string keys, a custom comparer, pooled row tables (their sorts keep their paths),
+    keys key_entries refuses, rows or k outside the job's TopKMinRows / TopKMaxFraction, and a
+    key column of one value (seen after the select's first pass)."""
+    from ..ops import topk as TK
+    from ..ops import tuning
+    t = _check(_one(inputs))
+    k = take_op["count"]
+    r = getattr(v, "runner", None)
+    tn = tuning.from_ctx(r.ctx) if r is not None else tuning.current()
+    if k <= 0 or k >= t.n or t.n < max(2, tn.topk_min_rows) or k > t.n * tn.topk_max_fraction:
+        raise NotTraceable("rows or k outside the top-k policy")
+    if sort_op.get("comparer") is not None:
+        raise NotTraceable("custom comparer")
+    if string_key(t, sort_op["key"]) is not None:
+        raise NotTraceable("string keys")
+    if _pooled_set(t, v) is not None:
+        raise NotTraceable("pooled row table")
+    e, b0, _ = key_entries(t, sort_op["key"], None, sort_op.get("descending", False))
+    out = TK.topk_entries(e, k, b0, equal_keys=False)
+    if out is None:
+        raise NotTraceable("all keys equal: the stable sort is the input order")
+    log.debug("sort + take as top-k: %s", TK.stats)
+    return t.take(_perm(out))
 
 
 def hash_keys(table: DeviceTable, key_fn):
@@ -1937,4 +1967,5 @@ def op_apply(op, inputs, v):
     return out if out is not None else res      # non-columnar results travel as host records
 
 
-OPS = {k[3:]: fn for k, fn in list(globals().items()) if k.startswith("op_")}
+# (op_sort_take is the executor's peephole over two ops, not an operator of its own)
+OPS = {k[3:]: fn for k, fn in list(globals().items()) if k.startswith("op_") and k != "op_sort_take"}

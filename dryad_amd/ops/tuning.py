@@ -5,6 +5,9 @@ thread, and operators read ``current()``.  Outside a job the defaults apply.
     GroupByAggregation   "auto" | "radix" | "sort": radix-partitioned LDS aggregation for a
                          single integer key (ops/radixagg.py) only for keys spanning >= 2^32
                          values ("auto"), for every large integer key ("radix"), or never ("sort").
+    TopKMinRows          OrderBy(...).Take(k) over at least this many rows of one partition ...
+    TopKMaxFraction      ... with k <= rows * fraction runs as a radix select of the k smallest
+                         sort entries (ops/topk.py) instead of a full sort and a slice.
 """
 from __future__ import annotations
 
@@ -16,6 +19,8 @@ from dataclasses import dataclass, replace
 @dataclass(frozen=True)
 class Tuning:
     groupby_aggregation: str = "auto"
+    topk_min_rows: int = 1 << 24
+    topk_max_fraction: float = 1 / 8
 
 
 _CUR: contextvars.ContextVar = contextvars.ContextVar("dryad_tuning", default=Tuning())
@@ -30,7 +35,10 @@ def from_ctx(ctx) -> Tuning:
     agg = props.get("GroupByAggregation") or "auto"
     if agg not in ("auto", "radix", "sort"):
         raise ValueError(f"GroupByAggregation must be auto, radix or sort, not {agg!r}")
-    return replace(Tuning(), groupby_aggregation=agg)
+    t = Tuning()
+    rows, frac = props.get("TopKMinRows"), props.get("TopKMaxFraction")
+    return replace(t, groupby_aggregation=agg, topk_min_rows=t.topk_min_rows if rows is None else int(rows),
+                   topk_max_fraction=t.topk_max_fraction if frac is None else float(frac))
 
 
 @contextlib.contextmanager

@@ -1009,15 +1009,33 @@ class GpuJobRunner:
             return inputs[0]             # the output stage of a streamed partitioning: committed by rename
         data = None
         with TRC.range(f"vertex {s.id}:{s.name}[{p}] v{version}"):
-            for i, op in enumerate(s.ops):
+            i = 0
+            while i < len(s.ops):
+                op = s.ops[i]
                 if cancel is not None and cancel.is_set():
                     raise VertexCancelled(f"{s.name}[{p}] v{version}")
                 args = inputs if i == 0 else [data]
+                if self._is_sort_take(s.ops, i, args):
+                    # OrderBy(...).Take(k): the k first rows by a radix select, not a full sort
+                    try:
+                        with TRC.range("sort_take"):
+                            data = G.op_sort_take(op, s.ops[i + 1], list(args), vctx)
+                        self.op_counts[("sort_take", "device")] += 1
+                        self.last_sort_path = "topk"
+                        i += 2
+                        continue
+                    except NotTraceable as e:       # nothing ran: the two ops as they are
+                        log.debug("%s: top-k select declined (%s)", s.name, e)
                 with TRC.range(op["op"]):
                     data = self._run_op(op, args, vctx, s)
+                i += 1
         if fault == "crash":        # the attempt dies after doing its work: its output must not be used
             raise VertexCrash(f"injected crash of {s.name}[{p}] v{version} (output discarded)")
         return data
+
+    def _is_sort_take(self, ops, i, args) -> bool:
+        return self.gpu_ok and i + 1 < len(ops) and ops[i]["op"] == "sort" and ops[i + 1]["op"] == "take" \
+            and bool(args) and all(isinstance(a, DeviceTable) for a in args)
 
     def _run_op(self, op, args, vctx, s):
         name = op["op"]
