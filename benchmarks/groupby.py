@@ -50,6 +50,8 @@ def main():
     ap.add_argument("--loopback-rank", type=int, default=0)
     ap.add_argument("--aggregation", choices=("auto", "radix", "sort"), default="auto",
                     help="GroupByAggregation context property (single integer key strategy)")
+    ap.add_argument("--matrix", choices=("off", "on"), default=None,
+                    help="GroupByMatrix context property (few distinct keys: int8 matrix-core aggregation)")
     ap.add_argument("--hbm-budget-gb", type=float, default=None,
                     help="HbmBudgetBytes: a partition past it is aggregated chunk by chunk (runtime/stream_agg.py), "
                          "e.g. --records-per-gpu 6.25e9 (400 GB) --hbm-budget-gb 60")
@@ -78,6 +80,8 @@ def main():
     if a.hbm_budget_gb:
         ctx.HbmBudgetBytes = int(a.hbm_budget_gb * 1e9)
     ctx.GroupByAggregation = a.aggregation
+    if a.matrix is not None:
+        ctx.GroupByMatrix = a.matrix
     n = int(a.records_per_gpu) * w.size
     src = f"gen://records64?count={n}&partitions={w.size}&keys={int(a.keys)}&seed=4242" + \
         ("&bounds=0" if a.no_bounds else "")
@@ -152,6 +156,7 @@ def main():
                        "declared by the generator" if a.source == "gen" else
                        "kept in the stored table's schema" if a.source == "partfile" else "carried by the host table"),
                    "hbm_budget_bytes": ctx.HbmBudgetBytes, "aggregation": a.aggregation,
+                   "group_path": ex.last_result.get("group_path"),
                    "streamed_aggregation": streamed[0] if streamed else None}})
 
 

@@ -55,6 +55,10 @@ def _run(cmd, verbose):
     return r
 
 
+# per-source compile flags on top of the common ones
+_KERNEL_FLAGS = {"matagg": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+
+
 def build_kernels(verbose: bool = False, force: bool = False) -> Path:
     """Compile csrc/kernels/*.hip for gfx950 into one shared library (object files cached)."""
     NATIVE_DIR.mkdir(parents=True, exist_ok=True)
@@ -67,7 +71,8 @@ def build_kernels(verbose: bool = False, force: bool = False) -> Path:
         o = objdir / (Path(s).stem + ".o")
         if force or _stale(o, [s] + hdrs):
             _run([_hipcc(), "-c", "-O3", "-std=c++17", f"--offload-arch={ARCH}", "-fPIC",
-                  "-munsafe-fp-atomics", "-Wno-unused-result", "-I", CSRC / "kernels", s, "-o", o], verbose)
+                  "-munsafe-fp-atomics", "-Wno-unused-result", *_KERNEL_FLAGS.get(Path(s).stem, []),
+                  "-I", CSRC / "kernels", s, "-o", o], verbose)
         objs.append(o)
     if force or _stale(KERNEL_LIB, objs):
         _run([_hipcc(), "-shared", "-fPIC", f"--offload-arch={ARCH}", *objs, "-o", KERNEL_LIB], verbose)

@@ -137,6 +137,9 @@ _DEFAULTS = dict(
     #                               into the exchange's send rows (no input table; a benchmark variant)
     GroupByAggregation="auto",    # single-integer-key GroupBy: "auto" (radix aggregation for keys spanning
     #                               >= 2^32 values), "radix" or "sort" (ops/tuning.py)
+    GroupByMatrix="off",          # GroupBy of one integer key with <= 256 sampled distinct keys and integer
+    #                               Count / Sum / Min / Max: "on" tries the int8 matrix-core aggregation
+    #                               (ops/matagg.py) before the LDS hash tables; "off" (ops/tuning.py)
     TopKMinRows=1 << 24,          # OrderBy(...).Take(k) on the GPU: a partition of at least this many rows ...
     TopKMaxFraction=1 / 8,        # ... with k <= rows * fraction selects its k smallest sort entries
     #                               (ops/topk.py) instead of sorting every row (ops/tuning.py)

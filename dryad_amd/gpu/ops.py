@@ -11,7 +11,8 @@ Hot paths are HIP kernels: key normalisation (dr_build_keys / dr_extract_keys), 
 destinations (dr_range_dest_u128), segmented reductions (dr_seg_reduce), merge-join expansion
 (dr_join_ranges / dr_join_emit), the hash join (dr_hj_*), whole-partition aggregates
 (dr_reduce_multi), row gathers (dr_gather_rows), the string-key sort and range destinations
-(dr_str_*, ops/strsort.py), the radix select behind OrderBy + Take (dr_topk_*, ops/topk.py) and the
+(dr_str_*, ops/strsort.py), the radix select behind OrderBy + Take (dr_topk_*, ops/topk.py), the
+matrix-core aggregation of few-key GroupBys (dr_matrix_aggregate, ops/matagg.py, opt-in) and the
 synthetic TeraSort store.
 Elementwise projections/predicates are traced user lambdas executed as PyTorch-ROCm tensor ops.
 """
@@ -1044,6 +1045,19 @@ def _fused_int64_groups(kcols, skeys, specs):
     return R.group_reduce_sorted(srt, specs, -(1 << 63))
 
 
+def _tuning(v):
+    from ..ops import tuning
+    r = getattr(v, "runner", None)
+    return tuning.from_ctx(r.ctx) if r is not None else tuning.current()
+
+
+def _group_path(v, path):
+    """Which aggregation served a group_partial stage, for the job result (``group_path``)."""
+    r = getattr(v, "runner", None)
+    if r is not None:
+        r.last_group_path = path
+
+
 def op_group_partial(op, inputs, v):
     t = _check(_one(inputs))
     d = op["decomp"]
@@ -1066,8 +1080,18 @@ def op_group_partial(op, inputs, v):
             # (``raw_ok``: a streamed GroupBy whose dense running state folds the rows itself)
             return _raw_partial(d, t, kcols[0], form)
         if nd <= R.HASH_AGG_MAX_KEYS and nd * 8 < m:
-            got = R.hash_aggregate(kcols[0], specs)
+            got, path = None, "hash"
+            if _tuning(v).groupby_matrix == "on":
+                # few distinct keys: count and sums on the matrix cores (exact int8 one-hot MFMA);
+                # None where that path does not serve, and the hash tables run as before
+                from ..ops import matagg as MA
+                if nd <= MA.MAX_GROUPS:
+                    got = MA.matrix_aggregate(kcols[0], specs)
+                    path = "matrix" if got is not None else path
+            if got is None:
+                got = R.hash_aggregate(kcols[0], specs)
             if got is not None:
+                _group_path(v, path)
                 keys, res = got
                 out = {"k0": keys}
                 for nm, r in zip(names, res):
@@ -1077,6 +1101,7 @@ def op_group_partial(op, inputs, v):
     # addressed by the low key bits (no sort, no hash, no gather)
     got = _dense_groups(kcols, skeys, specs, t.n)
     if got is not None:
+        _group_path(v, "dense")
         out = {"k0": got[0]}
         for nm, r in zip(names, got[1]):
             out[nm] = r
@@ -1084,6 +1109,7 @@ def op_group_partial(op, inputs, v):
     # one integer key, many distinct keys: radix-partitioned LDS aggregation (no sort, no gather)
     got = _radix_groups(kcols, skeys, specs, t.n, nd_est)
     if got is not None:
+        _group_path(v, "radix")
         out = {"k0": got[0]}
         for nm, r in zip(names, got[1]):
             out[nm] = r
@@ -1092,6 +1118,7 @@ def op_group_partial(op, inputs, v):
     # itself (no segment-id array, keys written at the group starts)
     fused = _fused_int64_groups(kcols, skeys, specs)
     if fused is not None:
+        _group_path(v, "fused")
         out = {"k0": fused[0]}
         for nm, r in zip(names, fused[1]):
             out[nm] = r
@@ -1099,10 +1126,12 @@ def op_group_partial(op, inputs, v):
     # one int64 key folding <= 3 columns: the values ride in the sort entries (no random gather)
     got = _payload_groups(kcols, skeys, specs, t.n)
     if got is not None:
+        _group_path(v, "payload")
         out = {"k0": got[0]}
         for nm, r in zip(names, got[1]):
             out[nm] = r
         return _partial_table(out, {}, d, 1, form)
+    _group_path(v, "sort")
     srt, seg, nseg, rows_at_start, starts = _group_keys(kcols, skeys)
     out, strs = _key_outputs(kcols, skeys, rows_at_start, srt, starts)
     # every aggregate in one fused segmented-reduce pass

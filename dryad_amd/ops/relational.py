@@ -419,6 +419,12 @@ def estimate_distinct(col: torch.Tensor, sample: int = 1 << 16) -> tuple[int, in
     return int(torch.unique(s_).numel()), int(s_.numel())
 
 
+def sample_distinct_values(col: torch.Tensor, sample: int = 1 << 16) -> torch.Tensor:
+    """The sorted distinct keys of the strided sample that estimate_distinct counts."""
+    step = max(1, col.shape[0] // sample)
+    return torch.unique(col[::step][:sample])
+
+
 def hash_aggregate(key: torch.Tensor, specs: list, capacity: int | None = None):
     """Low-cardinality GroupBy in one streaming pass (csrc/kernels/hashagg.hip).
 

@@ -5,6 +5,12 @@ thread, and operators read ``current()``.  Outside a job the defaults apply.
     GroupByAggregation   "auto" | "radix" | "sort": radix-partitioned LDS aggregation for a
                          single integer key (ops/radixagg.py) only for keys spanning >= 2^32
                          values ("auto"), for every large integer key ("radix"), or never ("sort").
+    GroupByMatrix        "off" | "on": a GroupBy of one integer key whose sample shows <= 256 distinct
+                         keys, with integer Count / Sum / Min / Max only, tries the exact int8
+                         one-hot MFMA aggregation (ops/matagg.py, csrc/kernels/matagg.hip) before
+                         the LDS hash tables.  "off" by default: at 1e9 rows it is 1.6x faster than
+                         the hash tables with 16 keys, level at 64 and 2.8x slower at 256
+                         (profiles/matagg_bw.log).
     TopKMinRows          OrderBy(...).Take(k) over at least this many rows of one partition ...
     TopKMaxFraction      ... with k <= rows * fraction runs as a radix select of the k smallest
                          sort entries (ops/topk.py) instead of a full sort and a slice.
@@ -19,6 +25,7 @@ from dataclasses import dataclass, replace
 @dataclass(frozen=True)
 class Tuning:
     groupby_aggregation: str = "auto"
+    groupby_matrix: str = "off"
     topk_min_rows: int = 1 << 24
     topk_max_fraction: float = 1 / 8
 
@@ -35,9 +42,13 @@ def from_ctx(ctx) -> Tuning:
     agg = props.get("GroupByAggregation") or "auto"
     if agg not in ("auto", "radix", "sort"):
         raise ValueError(f"GroupByAggregation must be auto, radix or sort, not {agg!r}")
+    mat = props.get("GroupByMatrix") or "off"
+    if mat not in ("off", "on"):
+        raise ValueError(f"GroupByMatrix must be off or on, not {mat!r}")
     t = Tuning()
     rows, frac = props.get("TopKMinRows"), props.get("TopKMaxFraction")
-    return replace(t, groupby_aggregation=agg, topk_min_rows=t.topk_min_rows if rows is None else int(rows),
+    return replace(t, groupby_aggregation=agg, groupby_matrix=mat,
+                   topk_min_rows=t.topk_min_rows if rows is None else int(rows),
                    topk_max_fraction=t.topk_max_fraction if frac is None else float(frac))
 
 

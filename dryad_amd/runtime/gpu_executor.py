@@ -1321,6 +1321,7 @@ class GpuJobRunner:
                     phases={k: round(v, 4) for k, v in self.phases.items()},
                     read=dict(bytes=self.read_stats.bytes, seconds=round(self.read_stats.seconds, 4)),
                     sort_path=getattr(self, "last_sort_path", None),
+                    group_path=getattr(self, "last_group_path", None),
                     exchange=(self.last_sort_stats.exchange_report() if getattr(self, "last_sort_stats", None)
                               is not None and self.last_sort_stats.rounds > 1 else None),
                     streamed={f"{k[0]}:{k[1]}": v for k, v in self.stream_stats.items()},
