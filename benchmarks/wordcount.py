@@ -1,7 +1,7 @@
 """WordCount benchmark (BASELINE.json config "WordCount via LocalJobSubmission on CPU (plumbing,
 runs without a GPU)"): MB/s of text counted, validated against collections.Counter.
 
-    python benchmarks/wordcount.py [--mb 256] [--procs 4] [--partitions 8] [--gpu]
+    python benchmarks/wordcount.py [--mb 256] [--procs 4] [--partitions 8] [--gpu] [--kernel auto|hash|sort]
 
 Default: the CPU process executor (LocalJobSubmission analog, ``--procs`` worker processes), the
 reference's own sample.  ``--gpu``: the same query through the GPU executor with the device
@@ -28,6 +28,8 @@ def main():
     ap.add_argument("--partitions", type=int, default=8)
     ap.add_argument("--steps", type=int, default=2)
     ap.add_argument("--gpu", action="store_true")
+    ap.add_argument("--kernel", choices=["auto", "hash", "sort"], default=None,
+                    help="WordCountKernel context property (fused LDS hash-table count, or token sort)")
     a = ap.parse_args()
     import dryad_amd as D
     from dryad_amd.models.wordcount import synthetic_corpus, word_count_query
@@ -40,6 +42,8 @@ def main():
     ctx = D.DryadLinqContext(platform="gpu") if a.gpu else D.DryadLinqContext(a.procs)
     if a.gpu:
         ctx.PartitionCount = a.partitions
+    if a.kernel:
+        ctx.WordCountKernel = a.kernel
     res = dict(word_count_query(ctx, uri))          # warmup (worker start, kernel load)
     times = []
     for _ in range(a.steps):

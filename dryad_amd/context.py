@@ -140,6 +140,8 @@ _DEFAULTS = dict(
     GroupByMatrix="off",          # GroupBy of one integer key with <= 256 sampled distinct keys and integer
     #                               Count / Sum / Min / Max: "on" tries the int8 matrix-core aggregation
     #                               (ops/matagg.py) before the LDS hash tables; "off" (ops/tuning.py)
+    WordCountKernel="auto",       # word counts of a text partition: "auto" / "hash" try the fused tokenise-and-
+    #                               count kernel with LDS hash tables first (ops/wordcount.py); "sort" (ops/tuning.py)
     TopKMinRows=1 << 24,          # OrderBy(...).Take(k) on the GPU: a partition of at least this many rows ...
     TopKMaxFraction=1 / 8,        # ... with k <= rows * fraction selects its k smallest sort entries
     #                               (ops/topk.py) instead of sorting every row (ops/tuning.py)

@@ -6,8 +6,9 @@ canonical sample) with a device tokeniser.
        .GroupBy(w => w.word, (k, g) => (k, g.Sum(c)))       # hash shuffle + final sum
 
 ``word_counts`` is a ``@device_function``: on the GPU executor the partition is a byte heap in
-HBM and tokenising / grouping runs as HIP kernels (ops/text.py: byte classification + compaction,
-64-bit token hashes, radix sort, segment counts, exact collision check); elsewhere it is the
+HBM and tokenising / grouping runs as HIP kernels (ops/text.py: the fused tokenise-and-count pass
+with LDS hash tables of ops/wordcount.py, or byte classification + compaction, 64-bit token hashes,
+radix sort and segment counts; an exact collision check either way); elsewhere it is the
 plain String.Split()-style host loop, so the LocalDebug oracle and the CPU executors give the
 reference answer.
 """

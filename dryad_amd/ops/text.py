@@ -127,8 +127,27 @@ def _word_groups(buf: torch.Tensor):
     return off, ln, order.index_select(0, starts), starts, nt
 
 
+# which kernel counted the words of the last word_count / word_count_table call: "hash"
+# (ops/wordcount.py) or "sort" (_word_groups)
+stats: dict = {}
+
+
+def _hash_groups(buf: torch.Tensor):
+    """(off, len, count) of the distinct words from the fused LDS hash-table pass, or None when
+    the WordCountKernel property says "sort", the table overflowed or two words shared a tag."""
+    from . import tuning
+    if tuning.current().wordcount_kernel == "sort":
+        return None
+    from . import wordcount as WC
+    return WC.count_words(buf)
+
+
 def word_count(buf: torch.Tensor) -> list:
     """[(word, count)] of the whitespace tokens in ``buf`` (device hash-group + exact check)."""
+    h = _hash_groups(buf)
+    stats["path"] = "sort" if h is None else "hash"
+    if h is not None:
+        return list(zip(gather_strings(buf, h[0], h[1]), h[2].cpu().tolist()))
     g = _word_groups(buf)
     if g is None:
         # 64-bit hash collision between different words: exact host path (never seen in practice)
@@ -150,6 +169,17 @@ def word_count_table(buf: torch.Tensor):
     check found a hash collision (the caller then takes the host path)."""
     from ..gpu.table import DeviceTable, Shape
     from . import channel as CH
+    h = _hash_groups(buf)
+    stats["path"] = "sort" if h is None else "hash"
+    if h is not None:
+        woff0, wl, counts = h
+        if woff0.numel() == 0:
+            return None
+        heap, woff = CH.compact_heap(buf, woff0, wl)
+        cnt = counts.to(torch.int32) if buf.shape[0] < (1 << 31) or int(counts.sum().item()) < (1 << 31) else counts
+        t = DeviceTable.from_columns({"Item1": woff, "Item1#len": wl, "Item2": cnt}, Shape("tuple", ["Item1", "Item2"]))
+        t.strs = {"Item1": heap}
+        return t
     g = _word_groups(buf)
     if g is None:
         return None

@@ -11,6 +11,14 @@ thread, and operators read ``current()``.  Outside a job the defaults apply.
                          the LDS hash tables.  "off" by default: at 1e9 rows it is 1.6x faster than
                          the hash tables with 16 keys, level at 64 and 2.8x slower at 256
                          (profiles/matagg_bw.log).
+    WordCountKernel      "auto" | "hash" | "sort": the word counts of a text partition (ops/text.py) from
+                         the fused tokenise-and-count pass with LDS hash tables (ops/wordcount.py,
+                         csrc/kernels/wordcount.hip) first ("auto", "hash": the sort path only when its
+                         table overflows or two words share a tag), or always by sorting token hashes.
+                         "auto" by default: on 1 GB of the benchmark's 50 000-word Zipf text the call
+                         takes 10.8 ms against 52.4 ms and the job step 56 ms against 97 ms; a text
+                         with more than 2^21 distinct words pays 10 ms for the pass that overflows
+                         (profiles/wordcount_bw.log, profiles/wordcount_job.log).
     TopKMinRows          OrderBy(...).Take(k) over at least this many rows of one partition ...
     TopKMaxFraction      ... with k <= rows * fraction runs as a radix select of the k smallest
                          sort entries (ops/topk.py) instead of a full sort and a slice.
@@ -26,6 +34,7 @@ from dataclasses import dataclass, replace
 class Tuning:
     groupby_aggregation: str = "auto"
     groupby_matrix: str = "off"
+    wordcount_kernel: str = "auto"
     topk_min_rows: int = 1 << 24
     topk_max_fraction: float = 1 / 8
 
@@ -46,8 +55,11 @@ def from_ctx(ctx) -> Tuning:
     if mat not in ("off", "on"):
         raise ValueError(f"GroupByMatrix must be off or on, not {mat!r}")
     t = Tuning()
+    wc = props.get("WordCountKernel") or t.wordcount_kernel
+    if wc not in ("auto", "hash", "sort"):
+        raise ValueError(f"WordCountKernel must be auto, hash or sort, not {wc!r}")
     rows, frac = props.get("TopKMinRows"), props.get("TopKMaxFraction")
-    return replace(t, groupby_aggregation=agg, groupby_matrix=mat,
+    return replace(t, groupby_aggregation=agg, groupby_matrix=mat, wordcount_kernel=wc,
                    topk_min_rows=t.topk_min_rows if rows is None else int(rows),
                    topk_max_fraction=t.topk_max_fraction if frac is None else float(frac))
 
