@@ -7,7 +7,7 @@ points.  Every timed iteration is a full DryadLINQ job through the GPU executor:
 gather of the K partial rows and the combine.  Points are generated once (gen://points ->
 hbm://) before timing.
 
-    python benchmarks/kmeans.py [--points-per-gpu 125e6] [--k 64] [--iters 5] [--warmup 1]
+    python benchmarks/kmeans.py [--points-per-gpu 125e6] [--k 64] [--dim 128] [--iters 5] [--warmup 1]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 benchmarks/kmeans.py
 """
 from __future__ import annotations
@@ -21,6 +21,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--points-per-gpu", type=float, default=125e6)
     ap.add_argument("--k", type=int, default=64)
+    ap.add_argument("--dim", type=int, default=128)
     ap.add_argument("--blobs", type=int, default=64)
     ap.add_argument("--iters", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
@@ -31,7 +32,7 @@ def main():
     from dryad_amd.models.kmeans import KMeansConfig, KMeansJob
     ctx = D.DryadLinqContext(platform="gpu")
     ctx.PartitionCount = w.size
-    cfg = KMeansConfig(points_per_partition=int(a.points_per_gpu), k=a.k, blobs=a.blobs)
+    cfg = KMeansConfig(points_per_partition=int(a.points_per_gpu), k=a.k, dim=a.dim, blobs=a.blobs)
     t_gen, job = timed(w, lambda: KMeansJob(ctx, cfg, partitions=w.size))
     cents = job.initial_centroids()
     for _ in range(a.warmup):
@@ -50,7 +51,7 @@ def main():
         "points_per_sec": round(n / s_it), "all_iteration_s": [round(t, 4) for t in times],
         "generate_s": round(t_gen, 3),
         "config": {"model": "k-means (DoWhile/ApplyPerPartition/Apply job per iteration)", "points": n,
-                   "dim": 128, "k": a.k, "parallelism": f"dp{w.size}"}})
+                   "dim": a.dim, "k": a.k, "parallelism": f"dp{w.size}"}})
 
 
 if __name__ == "__main__":

@@ -294,10 +294,11 @@ def op_read(op, inputs, v):
             return t
         if kind == "points":
             from ..ops import kmeans as KM
-            x = v.alloc_tensor((hi - lo, KM.DIM), torch.float32)
+            dim = int(q.get("dim", KM.DIM))
+            x = v.alloc_tensor((hi - lo, dim), torch.float32)
             KM.generate(x, lo, int(q.get("blobs", 64)), int(q.get("seed", 0)))
             from .. import types as T
-            return DeviceTable.from_columns({"x": x}, Shape("vector", ["x"], T.Vector(T.Float32, KM.DIM)))
+            return DeviceTable.from_columns({"x": x}, Shape("vector", ["x"], T.Vector(T.Float32, dim)))
         if kind == "records64":
             from ..ops import relational as R
             from ..models.records_cpu import FIELDS

@@ -348,8 +348,9 @@ class GenProvider(DataProvider):
     """Synthetic generator stores.  ``gen://range?count=N&partitions=P[&start=S]`` yields ints;
     ``gen://terasort?records=N&partitions=P&seed=S`` yields 100-byte TeraSort records (as bytes on
     the object path, generated directly in HBM by the GPU executor);
-    ``gen://points?count=N&partitions=P&blobs=B&seed=S`` yields 128-dim float32 blob points
-    (tuples on the object path, one [n, 128] HBM tensor on the GPU executor);
+    ``gen://points?count=N&partitions=P&blobs=B&seed=S[&dim=D]`` yields D-dim float32 blob points,
+    D = 128 by default, 1 .. 512 on the GPU executor (tuples on the object path, one [n, D] HBM
+    tensor on the GPU executor);
     ``gen://records64?count=N&partitions=P&keys=K&seed=S[&cols=C]`` yields 64-byte records of 8
     int64 fields (Key uniform in [0, K), V1..V7 31-bit values), columnar in HBM; ``&mode=dim``
     makes it a dimension table (keys a bijection of [0, K), payload a function of the key);
@@ -367,7 +368,7 @@ class GenProvider(DataProvider):
         if kind == "terasort":
             return p, int(q.get("records", 0)) * 100
         if kind == "points":
-            return p, int(q.get("count", 0)) * 4 * 128
+            return p, int(q.get("count", 0)) * 4 * int(q.get("dim", 128))
         if kind == "records64":
             return p, int(q.get("count", 0)) * 8 * int(q.get("cols", 8))
         if kind == "names":
@@ -380,8 +381,9 @@ class GenProvider(DataProvider):
 
     def schema(self, uri):
         from .. import types as T
-        kind, _ = self._args(uri)
-        dt = {"range": T.Int32, "terasort": T.Pickle, "points": T.Vector(T.Float32, 128)}.get(kind)
+        kind, q = self._args(uri)
+        dt = {"range": T.Int32, "terasort": T.Pickle,
+              "points": T.Vector(T.Float32, int(q.get("dim", 128)))}.get(kind)
         if kind == "records64":
             from ..models.records_cpu import FIELDS
             ncols = int(self._args(uri)[1].get("cols", 8))
@@ -411,7 +413,8 @@ class GenProvider(DataProvider):
             return gen_records(lo, hi - lo, int(q.get("seed", 0)))
         if kind == "points":
             from ..models.kmeans_cpu import gen_point_records
-            return gen_point_records(lo, hi - lo, int(q.get("blobs", 64)), int(q.get("seed", 0)))
+            return gen_point_records(lo, hi - lo, int(q.get("blobs", 64)), int(q.get("seed", 0)),
+                                     int(q.get("dim", 128)))
         if kind == "records64":
             from ..models.records_cpu import gen_records
             from ..models.records_cpu import dim_multiplier

@@ -10,7 +10,8 @@ Here the same query shape runs on the GPU executor:
 
 * ``partial_sums`` is a ``@device_function``: on each GPU it is ONE fused HIP kernel over the
   HBM-resident partition (f32 MFMA distance tiles, in-lane argmin, LDS-privatised sums; see
-  csrc/kernels/kmeans.hip) returning a K-row table (cluster, count, f64 sums);
+  csrc/kernels/kmeans.hip, and kmeans_dim.hip for ``KMeansConfig.dim`` other than 128) returning
+  a K-row table (cluster, count, f64 sums);
 * the K-row partials of all partitions are gathered and ``combine`` divides sums by counts;
 * the point table is materialised once in HBM (``hbm://``) and re-read by every iteration, so an
   iteration moves only K x 128 centroids plus K partial rows per GPU.
@@ -35,14 +36,19 @@ POINT_T = T.Vector(T.Float32, DIM)
 _WS: dict = {}
 
 
+def point_type(dim: int = DIM):
+    """The record type of a ``dim``-wide point or centroid."""
+    return POINT_T if dim == DIM else T.Vector(T.Float32, dim)
+
+
 def _step(x: torch.Tensor, c: torch.Tensor):
     """(sums f64 [K, D], counts i64 [K]) for one partition: HIP kernel on the GPU, torch on CPU."""
     if x.is_cuda:
         from ..ops import kmeans as KM
-        key = (x.device, c.shape[0])
+        key = (x.device, c.shape[0], x.shape[1])
         ws = _WS.get(key)
         if ws is None or ws.assign.shape[0] < x.shape[0]:
-            ws = _WS[key] = KM.KMeansWorkspace(x.shape[0], c.shape[0], x.device)
+            ws = _WS[key] = KM.KMeansWorkspace(x.shape[0], c.shape[0], x.device, dim=x.shape[1])
         sums, counts, _ = KM.step(x, c, ws)
         return sums.clone(), counts.clone()
     xd, cd = x.double(), c.double()
@@ -79,7 +85,7 @@ def combine(parts: DeviceTable, cents: DeviceTable) -> DeviceTable:
         0, ids, parts.col(2).to(dev).double())
     nd = n.to(torch.float64).unsqueeze(1)
     new = torch.where(nd > 0, s / nd.clamp_min(1), old.double()).to(torch.float32)
-    return DeviceTable.from_columns({"x": new}, Shape("vector", ["x"], POINT_T))
+    return DeviceTable.from_columns({"x": new}, Shape("vector", ["x"], point_type(old.shape[1])))
 
 
 def step_query(points, cents):
@@ -91,6 +97,7 @@ def step_query(points, cents):
 class KMeansConfig:
     points_per_partition: int = 125_000_000     # 8 GPUs -> 1e9 points x 128 dims (512 GB f32)
     k: int = 64
+    dim: int = DIM
     blobs: int = 64
     seed: int = 0x6B6D
     iterations: int = 5
@@ -113,7 +120,7 @@ class KMeansJob:
         n = cfg.points_per_partition * self.partitions
         self.n = n
         self.source_uri = (f"gen://points?count={n}&partitions={self.partitions}&blobs={cfg.blobs}"
-                           f"&seed={cfg.seed}")
+                           f"&seed={cfg.seed}" + (f"&dim={cfg.dim}" if cfg.dim != DIM else ""))
         pts = ctx.FromStore(self.source_uri)
         if materialize and not getattr(ctx, "LocalDebug", False):
             uri = f"{ctx.StorageScheme}://kmeans_points_{abs(hash(self.source_uri)) % 10**8}" \
@@ -124,10 +131,10 @@ class KMeansJob:
 
     def initial_centroids(self) -> list:
         """The first K generated points (deterministic, identical on every rank)."""
-        return [tuple(r) for r in gen_points(0, self.cfg.k, self.cfg.blobs, self.cfg.seed).tolist()]
+        return [tuple(r) for r in gen_points(0, self.cfg.k, self.cfg.blobs, self.cfg.seed, self.cfg.dim).tolist()]
 
     def iterate(self, cents: list) -> list:
-        c = self.ctx.FromEnumerable(cents, dtype=POINT_T)
+        c = self.ctx.FromEnumerable(cents, dtype=point_type(self.cfg.dim))
         return list(step_query(self.points, c))
 
     def run(self) -> KMeansResult:
@@ -147,7 +154,7 @@ class KMeansJob:
         """Same iteration through the ``DoWhile`` operator (client loop, one job per iteration)."""
         cfg = self.cfg
         state = {"i": 0}
-        c0 = self.ctx.FromEnumerable(self.initial_centroids(), dtype=POINT_T)
+        c0 = self.ctx.FromEnumerable(self.initial_centroids(), dtype=point_type(cfg.dim))
 
         def body(before):
             return step_query(self.points, before)
@@ -164,8 +171,8 @@ def reference(cfg: KMeansConfig, partitions: int, iterations: int | None = None)
     """numpy float64 k-means over the same generated points (test oracle for small configs)."""
     from .kmeans_cpu import step_reference
     n = cfg.points_per_partition * partitions
-    x = gen_points(0, n, cfg.blobs, cfg.seed)
-    c = gen_points(0, cfg.k, cfg.blobs, cfg.seed).astype(np.float64)
+    x = gen_points(0, n, cfg.blobs, cfg.seed, cfg.dim)
+    c = gen_points(0, cfg.k, cfg.blobs, cfg.seed, cfg.dim).astype(np.float64)
     for _ in range(iterations or cfg.iterations):
         s, cnt = step_reference(x, c.astype(np.float32))
         c = np.where(cnt[:, None] > 0, s / np.maximum(cnt, 1)[:, None], c)

@@ -1,5 +1,5 @@
 """Host (numpy) twin of the k-means point generator (``kmeans_gen_kernel`` in
-csrc/kernels/kmeans.hip) and a float64 reference step, used by the object/CPU executors reading
+csrc/kernels/kmeans.hip, ``kmd_gen_kernel`` in kmeans_dim.hip for widths other than 128) and a float64 reference step, used by the object/CPU executors reading
 ``gen://points`` and by tests."""
 from __future__ import annotations
 
@@ -15,9 +15,10 @@ def _u01(z: np.ndarray) -> np.ndarray:
 
 
 def gen_points(first: int, n: int, blobs: int, seed: int, dim: int = DIM) -> np.ndarray:
-    """Points first..first+n-1 as float32 [n, dim] (bit-identical to the GPU generator)."""
-    if dim != DIM:
-        raise ValueError("the point generator is defined for dim=128")
+    """Points first..first+n-1 as float32 [n, dim] (bit-identical to the GPU generator).  The
+    formula indexes by dimension, so a narrower set is the leading columns of a wider one."""
+    if dim < 1:
+        raise ValueError(f"the point dimension must be positive (dim = {dim})")
     i = np.arange(first, first + n, dtype=np.uint64)[:, None]
     d = np.arange(dim, dtype=np.uint64)[None, :]
     s = np.uint64(seed & (2**64 - 1))
@@ -30,8 +31,8 @@ def gen_points(first: int, n: int, blobs: int, seed: int, dim: int = DIM) -> np.
     return (centre + np.float32(0.2) * noise).astype(np.float32)
 
 
-def gen_point_records(first: int, n: int, blobs: int, seed: int) -> list:
-    return [tuple(r) for r in gen_points(first, n, blobs, seed).tolist()]
+def gen_point_records(first: int, n: int, blobs: int, seed: int, dim: int = DIM) -> list:
+    return [tuple(r) for r in gen_points(first, n, blobs, seed, dim).tolist()]
 
 
 def step_reference(points: np.ndarray, centroids: np.ndarray):
