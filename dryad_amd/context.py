@@ -142,6 +142,9 @@ _DEFAULTS = dict(
     #                               (ops/matagg.py) before the LDS hash tables; "off" (ops/tuning.py)
     WordCountKernel="auto",       # word counts of a text partition: "auto" / "hash" try the fused tokenise-and-
     #                               count kernel with LDS hash tables first (ops/wordcount.py); "sort" (ops/tuning.py)
+    GroupByKeyHash="off",         # GroupBy over a string, composite or wide key, Distinct over records with
+    #                               string fields: "on" / "auto" try the tag-and-verify hash aggregation with
+    #                               LDS tables (ops/keyhash.py) before the fingerprint sort (ops/tuning.py)
     TopKMinRows=1 << 24,          # OrderBy(...).Take(k) on the GPU: a partition of at least this many rows ...
     TopKMaxFraction=1 / 8,        # ... with k <= rows * fraction selects its k smallest sort entries
     #                               (ops/topk.py) instead of sorting every row (ops/tuning.py)

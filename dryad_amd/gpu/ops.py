@@ -893,13 +893,14 @@ def _agg_value(agg, t):
     return r.t
 
 
-def _key_cols(t, key_fn):
-    """Group key columns; string fields become Rabin fingerprints (skeys[i] = their StrCol).
+def _key_cols(t, key_fn, fingerprint=True):
+    """Group key columns; string fields become Rabin fingerprints (skeys[i] = their StrCol), or
+    stay None until the sort path asks for them (``fingerprint=False``, TR.fingerprint_strings).
     Also returns how the host path represents the key ("single" or "tuple")."""
     res = TR.call(key_fn, t)
     if isinstance(res, TR.RecProxy) and t.shape.kind == "dataclass":
         raise NotTraceable("record-valued group key")
-    cols, skeys = TR.eq_key_columns(res, t)
+    cols, skeys = TR.eq_key_columns(res, t, fingerprint)
     form = "tuple" if isinstance(res, (tuple, TR.RecProxy)) else "single"
     return cols, skeys, form
 
@@ -1046,6 +1047,24 @@ def _fused_int64_groups(kcols, skeys, specs):
     return R.group_reduce_sorted(srt, specs, -(1 << 63))
 
 
+def _keyhash_groups(kcols, skeys, specs, n, mode):
+    """(first rows, aggregate columns) through ops/keyhash.py (tag-and-verify hash aggregation with
+    LDS tables, no fingerprints and no sort) for a string, composite or wide key, else None.
+    ``mode``: the GroupByKeyHash property; "auto" serves only large partitions whose sampled
+    distinct estimate is below RAW_PARTIAL_FRACTION of the rows (mostly distinct keys sort)."""
+    if mode == "off" or (len(kcols) == 1 and skeys[0] is None):
+        return None
+    from ..ops import keyhash as KH
+    parts = [c if sk is None else (sk.heap, sk.off, sk.len) for c, sk in zip(kcols, skeys)]
+    cap = None
+    if mode == "auto":
+        est = KH.estimate_distinct(parts, n) if n >= (1 << 16) else None
+        cap = KH.capacity_for(est) if est is not None and est < RAW_PARTIAL_FRACTION * n else None
+        if cap is None:
+            return None
+    return KH.key_aggregate(parts, specs, n, capacity=cap)
+
+
 def _tuning(v):
     from ..ops import tuning
     r = getattr(v, "runner", None)
@@ -1066,7 +1085,8 @@ def op_group_partial(op, inputs, v):
         raise NotTraceable("aggregate not supported on the device")
     if t.n == 0:
         raise NotTraceable("empty partition")
-    kcols, skeys, form = _key_cols(t, op["key"])
+    keyhash = _tuning(v).groupby_keyhash
+    kcols, skeys, form = _key_cols(t, op["key"], fingerprint=keyhash == "off")
     specs, names = _group_specs(d, t)
     # low-cardinality integer keys: one streaming pass into LDS hash tables (no sort)
     nd_est = None
@@ -1132,7 +1152,17 @@ def op_group_partial(op, inputs, v):
         for nm, r in zip(names, got[1]):
             out[nm] = r
         return _partial_table(out, {}, d, 1, form)
+    # a string, composite or wide key: tags of the key parts in LDS hash tables, every row verified
+    # against its group's first row (no fingerprints, no sort, no gather)
+    got = _keyhash_groups(kcols, skeys, specs, t.n, keyhash)
+    if got is not None:
+        _group_path(v, "keyhash")
+        out, strs = _key_outputs(kcols, skeys, got[0])
+        for nm, r in zip(names, got[1]):
+            out[nm] = r
+        return _partial_table(out, strs, d, len(kcols), form)
     _group_path(v, "sort")
+    kcols = TR.fingerprint_strings(kcols, skeys)
     srt, seg, nseg, rows_at_start, starts = _group_keys(kcols, skeys)
     out, strs = _key_outputs(kcols, skeys, rows_at_start, srt, starts)
     # every aggregate in one fused segmented-reduce pass
@@ -1261,8 +1291,22 @@ def final_reduce(t, d):
     return _group_result(d, keys, vals, nseg, t.shape.pytype.key_form)
 
 
-def _group_result(d, keys, vals, nseg, form="single"):
-    """Substitute the per-group key/aggregate columns into the result-selector template."""
+def _nested(res) -> bool:
+    return isinstance(res, tuple) and not hasattr(res, "_fields") and any(isinstance(x, tuple) for x in res)
+
+
+def _nested_records(res, proto) -> list:
+    """The records of a traced tuple that has tuple-valued fields (a composite group key handed
+    back whole): each field's own table as host objects, zipped.  A device table has one column
+    per field, so these records leave the device here, as every stage's output does in the end."""
+    if _nested(res):
+        return list(zip(*[_nested_records(x, proto) for x in res]))
+    return TR.to_table(res, proto).to_objects()
+
+
+def _group_result(d, keys, vals, nseg, form="single", records_ok=False):
+    """Substitute the per-group key/aggregate columns into the result-selector template.
+    ``records_ok``: a result with tuple-valued fields may come back as host records (a list)."""
     nkeys = len(keys)
     kv = [k if isinstance(k, TR.StrCol) else TR.Col(k) for k in keys]
     key = kv[0] if nkeys == 1 and form == "single" else tuple(kv)
@@ -1275,6 +1319,8 @@ def _group_result(d, keys, vals, nseg, form="single"):
         raise NotTraceable(f"result template: {ex}")
     k0 = keys[0].off if isinstance(keys[0], TR.StrCol) else keys[0]
     proto = DeviceTable(nseg, Shape("scalar", ["v"]), {"v": k0})
+    if records_ok and _nested(res):
+        return _nested_records(res, proto)
     return TR.to_table(res, proto)
 
 
@@ -1284,7 +1330,7 @@ def op_group_by(op, inputs, v):
     d = op.get("decomp")
     if d is None or op.get("elem") is not None:
         raise NotTraceable("non-decomposable GroupBy")
-    return _finish_group(d, op_group_partial(dict(op, decomp=d), inputs, v))
+    return _finish_group(d, op_group_partial(dict(op, decomp=d), inputs, v), records_ok=True)
 
 
 def _ordered_group_keys(kcols, skeys):
@@ -1333,7 +1379,7 @@ def op_ordered_group_by(op, inputs, v):
     return _finish_group(d, _partial_table(out, strs, d, len(kcols), form))
 
 
-def _finish_group(d, tb):
+def _finish_group(d, tb, records_ok=False):
     nkeys = tb.shape.pytype.nkeys
     keys = _key_values(tb, nkeys)
     vals = []
@@ -1345,7 +1391,7 @@ def _finish_group(d, tb):
             vals.append(col.to(torch.bool))
         else:
             vals.append(col)
-    return _group_result(d, keys, vals, tb.n, tb.shape.pytype.key_form)
+    return _group_result(d, keys, vals, tb.n, tb.shape.pytype.key_form, records_ok)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -1355,6 +1401,14 @@ def op_distinct(op, inputs, v):
         raise NotTraceable("custom comparer")
     if t.n <= 1:
         return t
+    if t.strs and t.heap is None and _tuning(v).groupby_keyhash != "off":
+        # records with string fields: every field a key part of the hash aggregation, one count
+        from ..ops import keyhash as KH
+        fields = [TR._field(t, f) for f in t.shape.fields]
+        got = KH.key_aggregate([(f.heap, f.off, f.len) if isinstance(f, TR.StrCol) else f.t for f in fields],
+                               [("count", None, torch.int64)], t.n)
+        if got is not None:
+            return t.take(got[0])
     e, b0, lo_mask, packed = _record_entries(t)
     srt = S.sort_entries_hybrid(e, b0)
     seg, _, starts = R.segment_ids(srt, lo_mask)

@@ -348,11 +348,12 @@ def _record_table(vals: dict, shape, n, dev) -> DeviceTable:
     return t
 
 
-def eq_key_columns(res, table: DeviceTable):
+def eq_key_columns(res, table: DeviceTable, fingerprint: bool = True):
     """Key columns for equality-only consumers (GroupBy, HashPartition, Join): a string field is
     replaced by its Rabin-64 fingerprint column (ops/fingerprint.py).  Returns (cols, strkeys)
     with strkeys[i] the StrCol behind cols[i] (None for plain columns); callers must verify that
-    rows sharing a fingerprint hold equal strings.  Byte-string row keys stay NotTraceable here."""
+    rows sharing a fingerprint hold equal strings.  Byte-string row keys stay NotTraceable here.
+    ``fingerprint=False`` leaves cols[i] None for string fields (fingerprint_strings fills them in)."""
     if isinstance(res, RecProxy) and table.strs:
         items = [_field(table, f) for f in table.shape.fields]
     elif isinstance(res, StrCol):
@@ -364,16 +365,21 @@ def eq_key_columns(res, table: DeviceTable):
         if kind != "cols":
             raise NotTraceable("byte-string key")
         return spec, [None] * len(spec)
-    from ..ops.fingerprint import rabin_strings
     cols, skeys = [], []
     for v in items:
         if isinstance(v, StrCol):
-            cols.append(rabin_strings(v.heap, v.off, v.len))
+            cols.append(None)
             skeys.append(v)
         else:
             cols.append(_as_col(v, table.n, table.device))
             skeys.append(None)
-    return cols, skeys
+    return (fingerprint_strings(cols, skeys) if fingerprint else cols), skeys
+
+
+def fingerprint_strings(cols, skeys):
+    """``cols`` with the Rabin-64 fingerprint column of skeys[i] wherever cols[i] is None."""
+    from ..ops.fingerprint import rabin_strings
+    return [rabin_strings(sk.heap, sk.off, sk.len) if c is None else c for c, sk in zip(cols, skeys)]
 
 
 def to_mask(res, table: DeviceTable) -> torch.Tensor:
